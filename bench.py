@@ -7,10 +7,21 @@ mesh of V = 1 M vertices / E = 6 M directed edges (BASELINE.json's metric).
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line (rank 0).  `value` = training iterations per second of the whole job,
-inputs resident in HBM; `roofline` = the dominant edge-aggregation kernel's ALGORITHMIC
-bytes per launch / its mean launch duration measured with HIP events over the timed region;
-`cpu_baseline` = the oracle's PyG-equivalent ATen path on this box's host cores on a bounded
-sample (a reported baseline, not the target).
+inputs resident in HBM; `ms_per_step` = milliseconds of one timed iteration.  A plain run does
+only that: set-up, W warm-up iterations, K timed ones, the line.
+
+    --dump-outputs DIR   after the timed iterations, write what the last one computed as
+                         DIR/<name>.npy (float32): its loss, the network output, the input
+                         gradient, the parameters, their gradients and the BatchNorm statistics
+                         (a fixed, seeded sample of the rows of an array where all of them would
+                         exceed 64 MB).  The inputs are seeded: two builds can be compared
+                         output for output.
+    --full               everything else as well: launch timing of the kernels (`roofline`,
+                         `aggregation_kernels`, `dense_products`: the dominant edge-aggregation
+                         kernel's ALGORITHMIC bytes per launch / its mean launch duration measured
+                         with HIP events), the other feature precision, the other vertex order,
+                         `distributed_estimate` and `cpu_baseline` (the oracle's PyG-equivalent
+                         ATen path on the host cores: a reported baseline, not the target).
 """
 from __future__ import annotations
 
@@ -119,7 +130,16 @@ def parse():
                          "statistics riding in the halo exchange (dist.part_chain: 44 collectives; the default)")
     ap.add_argument("--model", default="sgcn", choices=["sgcn", "mgcn"],
                     help="mgcn: BASELINE config c3 (3 pool levels, hierarchy from meshprep.DeviceMesh); not the headline metric")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel launch timing and rooflines, the other "
+                         "feature precision, the other vertex order, the 8-rank estimate and the CPU baseline (the --no-* "
+                         "switches above leave single legs out); a plain run times the workload and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed iteration computed as DIR/<name>.npy (float32, 64 MB at most)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def algorithmic_bytes(V: int, E: int, C: int, elem: int, n_epilogue: int) -> float:
@@ -369,8 +389,61 @@ class TraceTimer:
         return out
 
 
-def timed_run(trainer, args, device, world, with_timer: bool):
-    """W untimed + exactly K timed iterations between barrier+synchronize brackets; max over ranks."""
+#: --dump-outputs writes at most this many bytes in all
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def collect_outputs(trainer, loss, out):
+    """What the last timed iteration left for a caller of the trainer, copied to the host as float32 arrays by name: its
+    loss, the network output (one array per level for the MGCN), the gradient of the network input z1 (accumulated over
+    every iteration of the run), the parameters and their gradients after it, and the BatchNorm running statistics."""
+    arrays = {}
+    if torch.is_tensor(loss):
+        arrays["loss"] = loss.detach().reshape(1)
+    outs = out if isinstance(out, (list, tuple)) else [out]
+    for i, o in enumerate(outs):
+        if torch.is_tensor(o):
+            arrays["output" if len(outs) == 1 else f"output_level{i}"] = o.detach()
+    for holder in (getattr(trainer, "_data", None), getattr(getattr(trainer, "mesh", None), "data", None)):
+        g = getattr(getattr(holder, "z1", None), "grad", None)
+        if g is not None:
+            arrays["z1_grad"] = g.detach()
+            break
+    model = trainer.model
+    for n, p in model.named_parameters():
+        arrays[f"param.{n}"] = p.detach()
+        if p.grad is not None:
+            arrays[f"grad.{n}"] = p.grad.detach()
+    for n, b in model.named_buffers():
+        if n.endswith(("running_mean", "running_var")):
+            arrays[f"buffer.{n}"] = b.detach()
+    return {k: v.float().cpu().numpy() for k, v in arrays.items()}
+
+
+def write_outputs(arrays, out_dir):
+    """DIR/<name>.npy for every array.  Where all of them would exceed DUMP_LIMIT_BYTES, the arrays with the most rows keep a
+    sample of their rows: the same rows (sorted, seeded by the array's name) in every run of the same arguments."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    rows = {k: (a.shape[0] if a.ndim else 1) for k, a in arrays.items()}
+    row_bytes = {k: a.nbytes // max(rows[k], 1) for k, a in arrays.items()}
+    cap = max(rows.values(), default=1)
+    while cap > 1 and sum(min(rows[k], cap) * row_bytes[k] for k in arrays) > DUMP_LIMIT_BYTES:
+        cap //= 2
+    sampled = []
+    for k, a in arrays.items():
+        if rows[k] > cap:
+            idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(rows[k], cap, replace=False))
+            a = a.reshape(rows[k], -1)[idx].reshape((cap,) + a.shape[1:])
+            sampled.append(k)
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log(f"outputs of the last timed iteration: {len(arrays)} arrays in {out_dir}"
+        + (f" ({', '.join(sampled)}: {cap} seeded sample rows each)" if sampled else ""))
+
+
+def timed_run(trainer, args, device, world, with_timer: bool, dump: bool = False):
+    """W untimed + exactly K timed iterations between barrier+synchronize brackets; max over ranks.  `dump`: the outputs of
+    the last timed iteration are copied to the host right after the timed region (timed_run.outputs, collect_outputs)."""
     from semigcn_amd import capi
 
     def sync():
@@ -429,11 +502,18 @@ def timed_run(trainer, args, device, world, with_timer: bool):
         c0 = dict(sgdist.collective_counts)
     bc0 = list(F_sg.block_calls)
     nr0 = list(sgdist.native_runs) if DIST_ON else [0, 0]
+    last_out = [None]
+    hook = trainer.model.register_forward_hook(lambda mod, inp, out: last_out.__setitem__(0, out)) if dump else None
+    loss = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        trainer.iteration_step()
+        loss = trainer.iteration_step()
     sync()
     dt = time.perf_counter() - t0
+    timed_run.outputs = None
+    if hook is not None:
+        hook.remove()
+        timed_run.outputs = collect_outputs(trainer, loss, last_out[0])
     # blocks that really ran below the C ABI (forward, backward) per iteration: what `per_module_path` claims, measured
     timed_run.block_calls = [round((F_sg.block_calls[i] - bc0[i]) / args.steps, 2) for i in range(2)]
     # passes (forward, backward) per iteration that ran as ONE sg_part_run call with the collectives enqueued by the library
@@ -945,17 +1025,21 @@ def main():
         raise SystemExit("--graph: one GPU only (a partitioned rank runs eagerly; its replay modes were retired in round 5)")
     if args.graph and args.warmup < 4:
         raise SystemExit("--graph: --warmup must be >= 4 (3 eager iterations + the capture)")
-    # byte accounting assumes the finest mesh only; inside a whole-iteration hipGraph launches cannot be timed
-    with_timer = not args.no_launch_timer and not args.graph and (args.model == "sgcn" or not DIST_ON)
+    # byte accounting assumes the finest mesh only; inside a whole-iteration hipGraph launches cannot be timed.
+    # Launch timing (roofline, per-kernel tables) is part of --full only: a plain run times the workload and nothing else
+    with_timer = args.full and not args.no_launch_timer and not args.graph and (args.model == "sgcn" or not DIST_ON)
 
     trainer, workload, agg_edges = build_trainer(args, dtypes[args.dtype], device, world, rank, mesh)
     log("model built; warm-up")
-    dt, timer = timed_run(trainer, args, device, world, with_timer)
+    dt, timer = timed_run(trainer, args, device, world, with_timer, dump=args.dump_outputs is not None)
     main_res = summarize(dt, timer, args, dtypes[args.dtype], mesh, world, agg_edges, trainer)
     log(f"timed region done: {main_res['ms_per_step']:.2f} ms/iteration ({args.dtype})")
+    if args.dump_outputs is not None and rank == 0:
+        write_outputs(timed_run.outputs, args.dump_outputs)
+    timed_run.outputs = None
 
     other = None
-    if not DIST_ON and args.model == "sgcn" and not args.single_dtype:
+    if args.full and not DIST_ON and args.model == "sgcn" and not args.single_dtype:
         # the same workload at the other feature precision, for the record (never `value`)
         del trainer
         torch.cuda.empty_cache()
@@ -973,7 +1057,7 @@ def main():
         torch.cuda.empty_cache()
 
     order2 = None
-    if not DIST_ON and args.model == "sgcn" and not args.no_second_order and not args.single_dtype:
+    if args.full and not DIST_ON and args.model == "sgcn" and not args.no_second_order and not args.single_dtype:
         # report BOTH vertex orders -- the same mesh renumbered at random (a raw scan) or, with --permute, in grid
         # order; the model's Morton processing order (networks.py) is what makes the two agree
         a2 = argparse.Namespace(**vars(args))
@@ -995,14 +1079,14 @@ def main():
             "metric": "GCN train iters/sec + edges-aggregated/sec, 1M-vert mesh",
             "value": main_res["value"], "unit": "iter/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": main_res["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": main_res["dtype"], "data": "synthetic",
+            "dtype": main_res["dtype"], "data": "synthetic", "full": bool(args.full),
             "config": {"workload": workload, "V": mesh.num_vertices, "E": mesh.num_edges,
                        "baseline_config": (("BASELINE configs[3] (SGCN, 1M-vertex mesh, bf16 features: bf16 storage of the "
                                             "per-vertex features, fp32 accumulation, fp32 parameters / loss / output); the "
-                                            "same workload at the reference's fp32 precision is in `fp32_features`")
+                                            "same workload at the reference's fp32 precision is in `fp32_features` (--full)")
                                            if args.dtype == "bf16" else
                                            ("BASELINE configs[3]'s mesh (SGCN, 1M vertices) at the reference's fp32 "
-                                            "precision; the bf16-feature variant named there is in `bf16_features`")) if (
+                                            "precision; the bf16-feature variant named there is in `bf16_features` (--full)")) if (
                            args.model == "sgcn" and (nu, nv) == (1000, 1000)) else None,
                        "mesh_recipe": ("SURVEY 8(d): closed torus grid, 0.15 * E_und random valid edge flips (valence 4..9), "
                                        if args.mesh_recipe == "survey" else
@@ -1040,12 +1124,12 @@ def main():
                                    "collectives_per_iteration": round(sum(coll.values()), 1), "collectives_by_kind": coll,
                                    "rank0_owned_rows": None if g is None else g.n_own,
                                    "rank0_halo_rows": None if g is None else g.n_halo}
-        if (not DIST_ON and world == 1 and args.model == "sgcn" and not args.no_distributed_estimate and not args.no_cpu_baseline
-                and mesh.num_vertices >= 500_000):
+        if (args.full and not DIST_ON and world == 1 and args.model == "sgcn" and not args.no_distributed_estimate
+                and not args.no_cpu_baseline and mesh.num_vertices >= 500_000):
             log("distributed estimate: two short child runs on the 1/8 mesh")
             line["distributed_estimate"] = distributed_estimate(args, main_res["ms_per_step"])
         line["cpu_baseline"] = cpu_baseline(args.cpu_sample, mesh.num_vertices, full=args.cpu_full, recipe=args.mesh_recipe) if (
-            not DIST_ON and not args.no_cpu_baseline) else None
+            args.full and not DIST_ON and not args.no_cpu_baseline) else None
         sys.stdout.flush()
         os.write(REAL_STDOUT, (json.dumps(line) + "\n").encode())
         if os.environ.get("SEMIGCN_BENCH_MARK"):          # the line is out: what follows cannot fail the attempt any more

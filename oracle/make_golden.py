@@ -281,6 +281,22 @@ def g6_bnf(ref, meshes, tmp):
     np.savez_compressed(os.path.join(OUT, "g6_bnf.npz"), **out)
 
 
+def g7_sgcn_train(ref, meshes):
+    """G7: the reference's own ``SingleScaleGCN`` (skip=True) in train mode on the torus, parameters from
+    ``GU.fill_state(seed=99)``, no dummy mask: the output tests/test_oracle.py holds the oracle's SGCN to."""
+    m = meshes["torus"]
+    net = ref.networks.SingleScaleGCN("cpu", skip=True)
+    GU.fill_state(net, seed=99)
+    net.train()
+
+    class D:
+        z1, x_pos, edge_index = torch.from_numpy(m.z1), torch.from_numpy(m.x_pos), torch.from_numpy(m.edge_index)
+
+    with torch.no_grad():
+        out = net(D, None)
+    np.savez_compressed(os.path.join(OUT, "g7_sgcn_train.npz"), **{"torus/skip1/train_seed99": out.numpy()})
+
+
 def main():
     only = sys.argv[sys.argv.index("--only") + 1].split(",") if "--only" in sys.argv else None
     warnings.simplefilter("ignore")
@@ -305,6 +321,8 @@ def main():
             g5_refine(ref, meshes, ref_meshes)
         if only is None or "g6" in only:
             g6_bnf(ref, meshes, tmp)
+        if only is None or "g7" in only:
+            g7_sgcn_train(ref, meshes)
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)) // 1024, "KiB")
 

@@ -356,7 +356,7 @@ def test_bench_gpus_2_starts_its_own_ranks():
     """`python bench.py --gpus 2` without a launcher: refuses when fewer devices are visible; with the share-one-GPU
     self-test switch it starts two ranks itself and rank 0 prints ONE line with n_gpus = 2."""
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-            "--mesh", "96x64", "--no-cpu-baseline", "--dtype", "fp32"]
+            "--mesh", "96x64", "--no-cpu-baseline", "--dtype", "fp32", "--full"]     # --full: the roofline below
     if torch.cuda.device_count() < 2:
         r = subprocess.run(base, env=_child_env(), capture_output=True, text=True, timeout=600)
         assert r.returncode != 0 and "refusing" in r.stderr and not r.stdout.strip()

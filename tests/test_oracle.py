@@ -153,22 +153,28 @@ def test_mgcn_oracle_vs_reference_golden():
     GU.check_grad_summary([(n, p.grad) for n, p in net.named_parameters() if p.grad is not None], golden, GRAD_TOL)
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="/root/reference not present (GPU box)")
 def test_oracle_vs_live_reference_sgcn(fixture_meshes):
-    ref = ref_shim.load()
+    """The oracle's SGCN in train mode against the reference's own (g7: its output, stored by oracle/make_golden.py);
+    bit for bit against the live reference classes where the reference tree is present."""
     m = fixture_meshes["torus"]
-    rnet = ref.networks.SingleScaleGCN("cpu", skip=True)
-    GU.fill_state(rnet, seed=99)
     onet = OM.SGCNOracle(skip=True)
-    onet.load_state_dict(rnet.state_dict())
+    GU.fill_state(onet, seed=99)
 
     class D:
         z1, x_pos, edge_index = torch.from_numpy(m.z1), torch.from_numpy(m.x_pos), torch.from_numpy(m.edge_index)
 
-    rnet.train(), onet.train()
-    a = rnet(D, None)
+    onet.train()
     b = onet(D.z1, D.x_pos, D.edge_index, None)
-    assert torch.equal(a, b)
+    assert rel(b.detach(), GU.load("g7_sgcn_train.npz")["torus/skip1/train_seed99"]) < MODEL_TOL
+    if ref_shim.available():
+        ref = ref_shim.load()
+        rnet = ref.networks.SingleScaleGCN("cpu", skip=True)
+        GU.fill_state(rnet, seed=99)
+        onet.load_state_dict(rnet.state_dict())
+        rnet.train()
+        a = rnet(D, None)
+        b = onet(D.z1, D.x_pos, D.edge_index, None)
+        assert torch.equal(a, b)
 
 
 # --------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 O=${1:-gpurun_out/configs.jsonl}
 : > $O
-run() { python bench.py "$@" --no-cpu-baseline --single-dtype --no-second-order 2>/dev/null | grep "^{" >> $O; }
+run() { python bench.py "$@" --full --no-cpu-baseline --single-dtype --no-second-order 2>/dev/null | grep "^{" >> $O; }
 # the reference's own sizes, EAGER (bench.py's default since round 4: runs of blocks below the C ABI) ...
 run --mesh 100x50 --dtype fp32 --steps 50 --warmup 5 --no-graph
 run --mesh 250x200 --dtype fp32 --steps 40 --warmup 5 --no-graph

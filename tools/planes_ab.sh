@@ -5,7 +5,7 @@ OUT=${1:-gpurun_out/r04/planes_ab.jsonl}
 mkdir -p $(dirname $OUT)
 for i in 1 2; do
   for m in "" "--no-planes"; do
-    python bench.py --steps 20 --warmup 5 --single-dtype --no-second-order --no-cpu-baseline --no-distributed-estimate $m 2>/dev/null | python -c "
+    python bench.py --full --steps 20 --warmup 5 --single-dtype --no-second-order --no-cpu-baseline --no-distributed-estimate $m 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 nar=[k for k in d['aggregation_kernels'] if k['C']<=64]

@@ -8,7 +8,7 @@ O=gpurun_out/$T
 cd $R
 mkdir -p $O
 for dt in bf16 fp32; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$dt -- python3 bench.py --dtype $dt --single-dtype --no-cpu-baseline --no-second-order --steps 5 --warmup 2 > $O/prof_$dt.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$dt -- python3 bench.py --full --dtype $dt --single-dtype --no-cpu-baseline --no-second-order --steps 5 --warmup 2 > $O/prof_$dt.log 2>&1
   for c in FETCH_SIZE WRITE_SIZE; do
     rocprofv3 --pmc $c --output-format csv -d $O/pmc_$dt/pmc_$c -- python3 bench.py --dtype $dt --single-dtype --no-cpu-baseline --no-second-order --no-launch-timer --steps 2 --warmup 1 > $O/pmc_${dt}_$c.log 2>&1
   done
