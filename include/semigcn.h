@@ -320,6 +320,42 @@ SG_API int sg_face_mask(const int64_t* faces, int64_t F, int64_t V, const uint64
                         int64_t W, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Scoring a completed mesh -- replaces check/dist_check.py:13-67
+ * (simple_mesh_distance / mesh_distance, which call pymeshlab's
+ * distance_from_reference_mesh filter from sgcn.py:183,193 and
+ * mgcn.py:175,201,213) and check/batch_dist_check.py.
+ *
+ * sg_surface_create: a bounding-volume hierarchy over the triangles of one
+ *   surface (vs float32 [V,3], faces int64 [F,3], device).  The surface owns
+ *   copies of its triangles; vs / faces are only borrowed until the stream has
+ *   run the build.  F == 0 or a face index outside [0, V) gives SG_ERR_INVALID
+ *   (checked on the device before any vertex is read through an index; the one
+ *   host synchronisation of the build).  Open and non-manifold surfaces and
+ *   zero-area triangles are allowed.
+ * sg_surface_query: for N points pts float32 [N,3]: dist [N] = distance to the
+ *   closest point of the surface, exact (no search bound); face [N] = the face
+ *   that point lies on: the one with the smallest float32 distance, the lowest
+ *   index on an exact tie; closest_or_null [N,3] = that point.  signed_dist != 0:
+ *   dist takes the sign of dot((b-a) x (c-a), p - closest) of that face, a zero
+ *   distance is +0.  Asynchronous; bit-reproducible (no atomics).
+ * sg_mesh_distance_reduce: one pass over the N vertices gt_vs [N,3] of gt with
+ *   q [N] (signed distances gt -> out): out (device, 4 doubles) =
+ *   (sum |q|, sum over the hole of |q|, hole count, diagonal of gt's vertex box).
+ *   hole[i] = hole_in[i] != 0 when hole_in is given, else q_org[i] > eps (q_org:
+ *   unsigned distances gt -> org); hole_out (nullable) receives it, 0 / 1.
+ *   hd_all = out[0] / N / out[3], hd_hole = out[1] / out[2] / out[3].  A fixed
+ *   summation order: deterministic.
+ * ------------------------------------------------------------------------- */
+typedef struct sg_surface sg_surface;
+SG_API int sg_surface_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, void* stream,
+                             sg_surface** out);
+SG_API int sg_surface_destroy(sg_surface* s);
+SG_API int sg_surface_query(const sg_surface* s, const float* pts, int64_t N, int signed_dist, float* dist,
+                            int32_t* face, float* closest_or_null, void* stream);
+SG_API int sg_mesh_distance_reduce(const float* q, const float* q_org, float eps, const uint8_t* hole_in,
+                                   const float* gt_vs, int64_t N, uint8_t* hole_out, double* out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Loss step of the training loop, fused -- replaces Models.compute_fn
  * (util/models.py:121-126), Loss.mask_pos_rec_loss (util/loss.py:14-34, 'rmse')
  * and Loss.mask_norm_rec_loss (util/loss.py:78-107, 'l1mae') as sgcn.py:130-132

@@ -188,6 +188,11 @@ _SIGNATURES = {
                               c_void_p]),
     "sg_mask_dilate": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "sg_face_mask": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sg_surface_create": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, POINTER(c_void_p)]),
+    "sg_surface_destroy": (c_int, [c_void_p]),
+    "sg_surface_query": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_mesh_distance_reduce": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                        c_void_p]),
 }
 
 _lib = None
@@ -1200,6 +1205,82 @@ def face_mask_bits(faces: torch.Tensor, vbits: torch.Tensor) -> torch.Tensor:
         _check(load().sg_face_mask(_ptr(faces), faces.shape[0], vbits.shape[0], _ptr(vbits), _ptr(out),
                                    vbits.shape[1], _stream(faces)), "sg_face_mask")
     return out
+
+
+class SurfaceHandle:
+    """Owns one sg_surface: the bounding-volume hierarchy over the triangles of one surface (the closest-point query of
+    check/dist_check.py:13-67)."""
+
+    def __init__(self, vs: torch.Tensor, faces: torch.Tensor):
+        _require_device(vs, "vs")
+        _require_device(faces, "faces")
+        if vs.dtype != torch.float32 or vs.dim() != 2 or vs.shape[1] != 3:
+            raise SemigcnLibraryError(f"vs must be float32 [V, 3], got {vs.dtype} {tuple(vs.shape)}")
+        if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
+            raise SemigcnLibraryError(f"faces must be int64 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+        vs, faces = vs.contiguous(), faces.contiguous()
+        self.device, self.num_vertices, self.num_faces = vs.device, vs.shape[0], faces.shape[0]
+        self._h = c_void_p(0)
+        out = c_void_p()
+        with _on_device(vs.device):
+            _check(load().sg_surface_create(_ptr(vs), vs.shape[0], _ptr(faces), faces.shape[0], _stream(vs), byref(out)),
+                   "sg_surface_create")
+        self._h = out
+
+    def query(self, pts: torch.Tensor, signed: bool = True, with_closest: bool = True):
+        """(dist float32 [N], face int32 [N], closest float32 [N, 3] or None) for the points pts float32 [N, 3]."""
+        _require_device(pts, "pts")
+        if pts.dtype != torch.float32 or pts.dim() != 2 or pts.shape[1] != 3:
+            raise SemigcnLibraryError(f"points must be float32 [N, 3], got {pts.dtype} {tuple(pts.shape)}")
+        if pts.device != self.device:
+            raise SemigcnLibraryError(f"points on {pts.device}, surface on {self.device}")
+        pts = pts.contiguous()
+        N = pts.shape[0]
+        dist = torch.empty(N, dtype=torch.float32, device=pts.device)
+        face = torch.empty(N, dtype=torch.int32, device=pts.device)
+        closest = torch.empty((N, 3), dtype=torch.float32, device=pts.device) if with_closest else None
+        with _on_device(pts.device):
+            _check(load().sg_surface_query(self._h, _ptr(pts), N, int(bool(signed)), _ptr(dist), _ptr(face), _ptr(closest),
+                                           _stream(pts)), "sg_surface_query")
+        return dist, face, closest
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            load().sg_surface_destroy(self._h)
+            self._h = c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def mesh_distance_reduce(q: torch.Tensor, gt_vs: torch.Tensor, q_org: Optional[torch.Tensor] = None, eps: float = 0.05,
+                         hole: Optional[torch.Tensor] = None):
+    """(sums float64 [4] = (sum |q|, sum |q[hole]|, n_hole, diag of gt_vs' box), hole bool [N]) on the device, in one fused
+    pass (sg_mesh_distance_reduce); hole = ``hole`` when given, else q_org > eps."""
+    for t, n in ((q, "q"), (gt_vs, "gt_vs"), (q_org, "q_org"), (hole, "hole")):
+        if t is not None:
+            _require_device(t, n)
+    N = q.numel()
+    if q.dtype != torch.float32 or gt_vs.dtype != torch.float32 or gt_vs.shape != (N, 3):
+        raise SemigcnLibraryError(f"mesh_distance_reduce: q float32 [N] and gt_vs float32 [N, 3] expected, got "
+                                  f"{q.dtype} {tuple(q.shape)} / {gt_vs.dtype} {tuple(gt_vs.shape)}")
+    if hole is None and (q_org is None or q_org.dtype != torch.float32 or q_org.numel() != N):
+        raise SemigcnLibraryError("mesh_distance_reduce: need hole bool [N] or q_org float32 [N]")
+    if hole is not None:
+        if hole.numel() != N:
+            raise SemigcnLibraryError(f"mesh_distance_reduce: hole has {hole.numel()} entries, gt {N} vertices")
+        hole = hole.reshape(-1).to(device=q.device, dtype=torch.bool).contiguous()
+    q, gt_vs = q.contiguous(), gt_vs.contiguous()
+    q_org = None if q_org is None else q_org.contiguous()
+    out = torch.empty(4, dtype=torch.float64, device=q.device)
+    hole_out = torch.empty(N, dtype=torch.bool, device=q.device)
+    with _on_device(q.device):
+        _check(load().sg_mesh_distance_reduce(_ptr(q), _ptr(q_org), float(eps), _ptr(hole), _ptr(gt_vs), N, _ptr(hole_out),
+                                              _ptr(out), _stream(q)), "sg_mesh_distance_reduce")
+    return out, hole_out
 
 
 # ---- one [ChebConv -> pool? -> BatchNorm -> activation] block per foreign call ---------------------------------------

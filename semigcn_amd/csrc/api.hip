@@ -499,6 +499,37 @@ SG_API int sg_face_mask(const int64_t* faces, int64_t F, int64_t V, const uint64
   return launch_face_mask(faces, F, V, vbits, fbits, W, (hipStream_t)stream);
 }
 
+// check/dist_check.py:13-67 (distance_from_reference_mesh, sgcn.py:183,193, mgcn.py:175,201,213)
+SG_API int sg_surface_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, void* stream, sg_surface** out) {
+  SG_REQUIRE(out != nullptr, "sg_surface_create: null out");
+  *out = nullptr;
+  SG_REQUIRE(F > 0 && V > 0, "sg_surface_create: need at least one face and one vertex (F = %lld, V = %lld)",
+             (long long)F, (long long)V);
+  SG_REQUIRE(vs && faces, "sg_surface_create: null pointer");
+  return surface_create(vs, V, faces, F, (hipStream_t)stream, out);
+}
+
+SG_API int sg_surface_destroy(sg_surface* s) {
+  destroy_surface(s);
+  return SG_OK;
+}
+
+SG_API int sg_surface_query(const sg_surface* s, const float* pts, int64_t N, int signed_dist, float* dist,
+                            int32_t* face, float* closest_or_null, void* stream) {
+  SG_REQUIRE(s != nullptr, "sg_surface_query: null surface");
+  SG_REQUIRE(N >= 0, "sg_surface_query: negative N");
+  if (N == 0) return SG_OK;
+  SG_REQUIRE(pts && dist && face, "sg_surface_query: null pointer");
+  return surface_query(s, pts, N, signed_dist, dist, face, closest_or_null, (hipStream_t)stream);
+}
+
+SG_API int sg_mesh_distance_reduce(const float* q, const float* q_org, float eps, const uint8_t* hole_in,
+                                   const float* gt_vs, int64_t N, uint8_t* hole_out, double* out, void* stream) {
+  SG_REQUIRE(N >= 0 && out, "sg_mesh_distance_reduce: bad argument");
+  SG_REQUIRE(N == 0 || (q && gt_vs && (hole_in || q_org)), "sg_mesh_distance_reduce: null pointer");
+  return mesh_distance_reduce(q, q_org, eps, hole_in, gt_vs, N, hole_out, out, (hipStream_t)stream);
+}
+
 SG_API int sg_mesh_loss_bwd_det(const float* pos, const int64_t* faces, const float* target_pos, const float* v_keep,
                                 const float* target_fn, const float* f_keep, const float* g, int64_t V, int64_t V_ext,
                                 int64_t F, const sg_pool* incidence, float* corner_scratch, float* grad_pos, void* stream_) {

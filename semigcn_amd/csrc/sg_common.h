@@ -345,6 +345,13 @@ int mesh_edges(const int64_t* faces, int64_t F, int64_t V, int64_t* edges_out, i
 int launch_mask_dilate(const Csr& c, const uint64_t* in, uint64_t* out, int64_t W, hipStream_t stream);
 int launch_face_mask(const int64_t* faces, int64_t F, int64_t V, const uint64_t* vbits, uint64_t* fbits, int64_t W,
                      hipStream_t stream);
+// csrc/mesh_dist.hip
+int surface_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, hipStream_t stream, sg_surface** out);
+void destroy_surface(sg_surface* s);
+int surface_query(const sg_surface* s, const float* pts, int64_t N, int signed_dist, float* dist, int32_t* face,
+                  float* closest, hipStream_t stream);
+int mesh_distance_reduce(const float* q, const float* q_org, float eps, const uint8_t* hole_in, const float* gt_vs,
+                         int64_t N, uint8_t* hole_out, double* out, hipStream_t stream);
 
 int launch_mesh_loss_bwd_corners(const float* pos, const int64_t* faces, const float* tfn, const float* fkeep, const float* g,
                                  int64_t F, float* corner, hipStream_t stream);
