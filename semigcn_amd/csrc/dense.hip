@@ -219,9 +219,15 @@ inline bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // compute-bound ones that the persistent 256 x 256 kernel does not serve
 constexpr int64_t kMfmaMaxWeightElems = 100000;
 
-// sum of n_slabs [N, Kp] slab partials (contiguous, slab stride N * Kp) in slab order -> out (row stride ldo); any shape
+// sum of n_slabs [N, Kp] slab partials (contiguous, slab stride N * Kp) in slab order -> out (row stride ldo); any shape.
+// Workgroups past the first `main_blocks` carry the conv-bias rider of the sink (GradSink::cs_*), one channel each, as the
+// reduce kernels of the other engines do: an engine that reports `sunk` owes the bias sums as well.
 __global__ __launch_bounds__(256) void slab_sum(const float* __restrict__ W, int n_slabs, int64_t elems, int Kp,
-                                                float* __restrict__ out, int64_t ldo, const GradSink sink) {
+                                                float* __restrict__ out, int64_t ldo, const GradSink sink, int main_blocks) {
+  if ((int)blockIdx.x >= main_blocks) {
+    colsum_ride(sink, (int)blockIdx.x - main_blocks);
+    return;
+  }
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= elems) return;
   float acc = 0.f;
@@ -406,7 +412,9 @@ int dense_tn(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, 
     if (rc != SG_OK) return rc;
     ++n_slabs;
   }
-  slab_sum<<<(int)((elems + 255) / 256), 256, 0, stream>>>(ws, n_slabs, elems, (int)Kp, out, ldo, sink ? *sink : GradSink{});
+  const int main_blocks = (int)((elems + 255) / 256);
+  slab_sum<<<main_blocks + ((sink && sink->cs_partial) ? sink->cs_C : 0), 256, 0, stream>>>(ws, n_slabs, elems, (int)Kp, out, ldo,
+                                                                                          sink ? *sink : GradSink{}, main_blocks);
   if (sunk) *sunk = sink != nullptr;
   SG_HIP_TRY(hipGetLastError());
   return SG_OK;
