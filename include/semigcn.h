@@ -392,6 +392,40 @@ SG_API int sg_mesh_loss_bwd(const float* pos, const int64_t* faces, const float*
                             int64_t F, float* grad_pos, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Bilateral face-normal filter and the -CAD loss term -- replaces Models.bnf
+ * (util/models.py:209-237) and Loss.fn_bnf_detach_loss (util/loss.py:197-253,
+ * 'l1mae') as sgcn.py:133-135, mgcn.py:146-148 and mgcn_wo_gt.py:116-118 call it.
+ *   pos [V,3] float32, faces int64 [F,3], f2f int64 [F,3] face ring padded with -1
+ *   (a -1 reads face F-1 with zero weight and counts in sigma_c, as in the reference).
+ * sg_bnf_filter: fn [F,3] = unit face normals of pos (compute_fn, util/models.py:121-126);
+ *           n_filtered [F,3] = `loop` rounds of the filter started from start_fn [F,3]
+ *           (NULL: from fn), weights exp(-d_c / 2 sigma_c^2) exp(-|dn|^2 / 2 sigma_s^2) fa[g];
+ *           sigma_c stays on the device.  loss_partial (may be NULL): nb = sg_bnf_blocks(F)
+ *           block partials of S_b = sum_f |n_filtered - fn|_1.  scratch: sg_bnf_scratch_bytes(F)
+ *           bytes, 16-byte aligned.  3 + loop launches, no atomics, fixed-order sums.
+ * sg_mesh_loss_cad_finalize: sg_mesh_loss_finalize with the term on top:
+ *           out[0] = w_pos sqrt(S_p / n_v + 1e-6) + k1 S_n / n_f + k2 S_b / F,
+ *           out[1..3] = d loss / d (S_p, S_n, S_b).  partial == NULL: the -CAD term alone
+ *           (out[0] = k2 S_b / F, out[1] = out[2] = 0).
+ * sg_mesh_loss_cad_bwd_det: sg_mesh_loss_bwd_det with both normal terms in its one pass over
+ *           the faces: g[1] keep_f sgn(fn - target_fn) + g[2] sgn(fn - n_filtered) (g: 3 floats on
+ *           the device; fn, n_filtered: as sg_bnf_filter wrote them; the filter carries no
+ *           gradient, util/loss.py:232).  target_fn and f_keep
+ *           may both be NULL, and V = 0 with target_pos = v_keep = NULL drops the position term.
+ * ------------------------------------------------------------------------- */
+SG_API int64_t sg_bnf_blocks(int64_t F);
+SG_API int64_t sg_bnf_scratch_bytes(int64_t F);
+SG_API int sg_bnf_filter(const float* pos, const int64_t* faces, const int64_t* f2f, int64_t V, int64_t F, int loop,
+                         float sigma_s, const float* start_fn, float* fn, float* n_filtered, float* loss_partial,
+                         void* scratch, void* stream);
+SG_API int sg_mesh_loss_cad_finalize(const float* partial, int64_t nb, float n_v, float n_f, float w_pos, float k1,
+                                     const float* bnf_partial, int64_t nb_bnf, int64_t F, float k2, float* out, void* stream);
+SG_API int sg_mesh_loss_cad_bwd_det(const float* pos, const int64_t* faces, const float* target_pos, const float* v_keep,
+                                    const float* target_fn, const float* f_keep, const float* fn, const float* n_filtered,
+                                    const float* g, int64_t V, int64_t V_ext, int64_t F, const sg_pool* incidence,
+                                    float* corner_scratch, float* grad_pos, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Launch tuning of the aggregation kernel (process-wide, not thread-safe; for
  * benchmarking -- results never depend on it).
  * ------------------------------------------------------------------------- */

@@ -138,6 +138,12 @@ _SIGNATURES = {
     "sg_input_prep_bwd_routed": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_int64, c_int, c_void_p]),
     "sg_mesh_loss_finalize": (c_int, [c_void_p, c_int64, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
+    "sg_bnf_blocks": (c_int64, [c_int64]),
+    "sg_bnf_scratch_bytes": (c_int64, [c_int64]),
+    "sg_bnf_filter": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_float] + [c_void_p] * 6),
+    "sg_mesh_loss_cad_finalize": (c_int, [c_void_p, c_int64, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_int64, c_float,
+                                          c_void_p, c_void_p]),
+    "sg_mesh_loss_cad_bwd_det": (c_int, [c_void_p] * 9 + [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_input_prep_blocks": (c_int64, [c_int64]),
     "sg_input_prep": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "sg_input_prep_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -1167,6 +1173,61 @@ def mesh_loss_bwd_det(pos, faces, target_pos, v_keep, target_fn, f_keep, g: torc
         _check(load().sg_mesh_loss_bwd_det(_ptr(_f32c(pos, "pos")), _ptr(faces), _ptr(target_pos), _ptr(v_keep),
                                            _ptr(target_fn), _ptr(f_keep), _ptr(_f32c(g, "g")), V, pos.shape[0], F,
                                            incidence._h, _ptr(corner), _ptr(grad), _stream(pos)), "sg_mesh_loss_bwd_det")
+    return grad
+
+
+def _i64c(t: torch.Tensor, name: str, rows: int) -> torch.Tensor:
+    _require_device(t, name)
+    if t.dtype != torch.int64 or not t.is_contiguous() or tuple(t.shape) != (rows, 3):
+        raise SemigcnLibraryError(f"{name} must be contiguous int64 [{rows}, 3], got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def bnf_filter(pos: torch.Tensor, faces: torch.Tensor, f2f: torch.Tensor, loop: int = 5, sigma_s: float = 0.3,
+               start_fn: Optional[torch.Tensor] = None, with_partials: bool = False):
+    """(fn [F,3], n_filtered [F,3], block partials of sum_f |n_filtered - fn|_1 or None): ``loop`` rounds of the bilateral
+    face-normal filter over the face ring ``f2f`` (util/models.py:209-237, util/loss.py:197-232), started from ``start_fn``
+    (None: the face normals of ``pos``).  3 + loop launches on the current stream, no host synchronisation."""
+    F = faces.shape[0]
+    _f32c(pos, "pos"), _i64c(faces, "faces", F), _i64c(f2f, "f2f", F)
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise SemigcnLibraryError(f"pos must be [V, 3], got {tuple(pos.shape)}")
+    if start_fn is not None and tuple(_f32c(start_fn, "fn").shape) != (F, 3):
+        raise SemigcnLibraryError(f"fn must be [{F}, 3], got {tuple(start_fn.shape)}")
+    fn = torch.empty((F, 3), dtype=torch.float32, device=pos.device)
+    nf = torch.empty((F, 3), dtype=torch.float32, device=pos.device)
+    part = torch.empty((_sizes("sg_bnf_blocks", F),), dtype=torch.float32, device=pos.device) if with_partials else None
+    scratch = torch.empty((_sizes("sg_bnf_scratch_bytes", F) // 4,), dtype=torch.float32, device=pos.device)
+    with _on_device(pos.device):
+        _check(load().sg_bnf_filter(_ptr(pos), _ptr(faces), _ptr(f2f), pos.shape[0], F, int(loop), float(sigma_s), _ptr(start_fn),
+                                    _ptr(fn), _ptr(nf), _ptr(part), _ptr(scratch), _stream(pos)), "sg_bnf_filter")
+    return fn, nf, part
+
+
+def mesh_loss_cad_finalize(partial: Optional[torch.Tensor], n_v: float, n_f: float, w_pos: float, k1: float,
+                           bnf_partial: torch.Tensor, num_faces: int, k2: float) -> torch.Tensor:
+    """float32 [4] = (w_pos sqrt(S_p / n_v + 1e-6) + k1 S_n / n_f + k2 S_b / F, d loss / d S_p, d S_n, d S_b); ``partial`` None:
+    the bilateral term alone."""
+    out = torch.empty((4,), dtype=torch.float32, device=bnf_partial.device)
+    with _on_device(out.device):
+        _check(load().sg_mesh_loss_cad_finalize(_ptr(partial), 0 if partial is None else partial.shape[0], float(n_v), float(n_f),
+                                                float(w_pos), float(k1), _ptr(bnf_partial), bnf_partial.shape[0], int(num_faces),
+                                                float(k2), _ptr(out), _stream(out)), "sg_mesh_loss_cad_finalize")
+    return out
+
+
+def mesh_loss_cad_bwd_det(pos, faces, target_pos, v_keep, target_fn, f_keep, fn, n_filtered, g: torch.Tensor,
+                          incidence: "PoolHandle") -> torch.Tensor:
+    """mesh_loss_bwd_det with the bilateral term (``fn`` against ``n_filtered``, scale g[2]) in the same pass over the faces;
+    ``target_pos`` / ``target_fn`` None: that term is absent."""
+    V, F = 0 if target_pos is None else target_pos.shape[0], faces.shape[0]
+    grad = torch.empty_like(pos)
+    corner = torch.empty((3 * F, 3), dtype=torch.float32, device=pos.device)
+    with _on_device(pos.device):
+        _check(load().sg_mesh_loss_cad_bwd_det(_ptr(_f32c(pos, "pos")), _ptr(faces), _ptr(target_pos), _ptr(v_keep),
+                                               _ptr(target_fn), _ptr(f_keep), _ptr(_f32c(fn, "fn")), _ptr(_f32c(n_filtered, "n_filtered")),
+                                               _ptr(_f32c(g, "g")), V, pos.shape[0], F, incidence._h, _ptr(corner), _ptr(grad),
+                                               _stream(pos)), "sg_mesh_loss_cad_bwd_det")
     return grad
 
 

@@ -746,6 +746,56 @@ SG_API int sg_mesh_loss_finalize(const float* partial, int64_t nb, float n_v, fl
   return launch_mesh_loss_finalize(partial, nb, n_v, n_f, w_pos, k1, out, (hipStream_t)stream);
 }
 
+// Models.bnf (util/models.py:209-237) / Loss.fn_bnf_detach_loss (util/loss.py:197-253): csrc/mesh_bnf.hip
+SG_API int64_t sg_bnf_blocks(int64_t F) { return F >= 0 ? bnf_blocks(F) : -1; }
+
+SG_API int64_t sg_bnf_scratch_bytes(int64_t F) { return F >= 0 ? bnf_scratch_bytes(F) : -1; }
+
+SG_API int sg_bnf_filter(const float* pos, const int64_t* faces, const int64_t* f2f, int64_t V, int64_t F, int loop,
+                         float sigma_s, const float* start_fn, float* fn, float* n_filtered, float* loss_partial,
+                         void* scratch, void* stream) {
+  SG_REQUIRE(V >= 0 && F >= 0 && F <= INT32_MAX / 4, "sg_bnf_filter: negative size or more than 2^29 faces");
+  SG_REQUIRE(loop >= 0, "sg_bnf_filter: negative loop count %d", loop);
+  SG_REQUIRE(sigma_s > 0.f, "sg_bnf_filter: sigma_s must be positive");
+  SG_REQUIRE(F == 0 || (pos && faces && f2f && fn && n_filtered && scratch && V > 0), "sg_bnf_filter: null pointer");
+  SG_REQUIRE(F == 0 || (fn != n_filtered && start_fn != n_filtered), "sg_bnf_filter: n_filtered must be a distinct array");
+  SG_REQUIRE(F == 0 || ((uintptr_t)scratch & 15) == 0, "sg_bnf_filter: scratch must be 16-byte aligned");
+  return launch_bnf_filter(pos, faces, f2f, V, F, loop, sigma_s, start_fn, fn, n_filtered, loss_partial, scratch,
+                           (hipStream_t)stream);
+}
+
+SG_API int sg_mesh_loss_cad_finalize(const float* partial, int64_t nb, float n_v, float n_f, float w_pos, float k1,
+                                     const float* bnf_partial, int64_t nb_bnf, int64_t F, float k2, float* out, void* stream) {
+  SG_REQUIRE(out && bnf_partial && nb_bnf > 0 && F > 0, "sg_mesh_loss_cad_finalize: bad argument");
+  SG_REQUIRE(!partial || (nb > 0 && n_v > 0.f && n_f >= 0.f), "sg_mesh_loss_cad_finalize: bad argument");
+  return launch_mesh_loss_cad_finalize(partial, nb, n_v, n_f, w_pos, k1, bnf_partial, nb_bnf, (float)F, k2, out,
+                                       (hipStream_t)stream);
+}
+
+SG_API int sg_mesh_loss_cad_bwd_det(const float* pos, const int64_t* faces, const float* target_pos, const float* v_keep,
+                                    const float* target_fn, const float* f_keep, const float* fn, const float* n_filtered,
+                                    const float* g, int64_t V, int64_t V_ext, int64_t F, const sg_pool* incidence,
+                                    float* corner_scratch, float* grad_pos, void* stream_) {
+  SG_REQUIRE(V >= 0 && F >= 0 && V_ext >= V && g && (V_ext == 0 || grad_pos), "sg_mesh_loss_cad_bwd_det: bad argument");
+  SG_REQUIRE((V == 0 || (pos && target_pos && v_keep)) && (F == 0 || (pos && faces && fn && n_filtered)) && !target_fn == !f_keep,
+             "sg_mesh_loss_cad_bwd_det: null pointer");
+  SG_REQUIRE(incidence && incidence->by_coarse.n_rows == V_ext && incidence->by_coarse.n_cols == 3 * F &&
+                 (F == 0 || corner_scratch),
+             "sg_mesh_loss_cad_bwd_det: incidence must map the 3F face corners onto V_ext vertices");
+  hipStream_t stream = (hipStream_t)stream_;
+  int rc = launch_mesh_loss_cad_bwd_corners(pos, faces, target_fn, f_keep, fn, n_filtered, g, F, corner_scratch, stream);
+  if (rc != SG_OK) return rc;
+  if (V_ext == 0) return SG_OK;
+  if (F == 0) {
+    SG_HIP_TRY(hipMemsetAsync(grad_pos, 0, (size_t)V_ext * 3 * sizeof(float), stream));
+  } else {   // grad[v] = sum over the corners incident to v, in CSR (ascending corner id) order
+    rc = run_csr(incidence->by_coarse, nullptr, nullptr, corner_scratch, 3, nullptr, 0, nullptr, 0, grad_pos, 3, 3, SG_F32,
+                 1.f, 0.f, 0.f, stream);
+    if (rc != SG_OK) return rc;
+  }
+  return launch_mesh_loss_bwd_vertex_add(pos, target_pos, v_keep, g, V, grad_pos, stream);
+}
+
 SG_API int sg_multi_add(int64_t n, const float* const* srcs, const int64_t* src_ld, const int64_t* rows, const int64_t* cols,
                         float* const* dsts, void* stream) {
   SG_REQUIRE(n >= 0 && n <= kMultiAddMax, "sg_multi_add: at most %d matrices per call", kMultiAddMax);

@@ -358,6 +358,16 @@ int launch_mesh_loss_bwd_corners(const float* pos, const int64_t* faces, const f
 int launch_mesh_loss_bwd_vertex_add(const float* pos, const float* tpos, const float* vkeep, const float* g, int64_t V,
                                     float* grad, hipStream_t stream);
 
+// mesh_bnf.hip
+int64_t bnf_blocks(int64_t F);
+int64_t bnf_scratch_bytes(int64_t F);
+int launch_bnf_filter(const float* pos, const int64_t* faces, const int64_t* f2f, int64_t V, int64_t F, int loop, float sigma_s,
+                      const float* start, float* fn, float* nf, float* lpart, void* scratch, hipStream_t stream);
+int launch_mesh_loss_cad_finalize(const float* partial, int64_t nb, float n_v, float n_f, float w_pos, float k1, const float* bpart,
+                                  int64_t nbb, float n_faces, float k2, float* out, hipStream_t stream);
+int launch_mesh_loss_cad_bwd_corners(const float* pos, const int64_t* faces, const float* tfn, const float* fkeep, const float* fn,
+                                     const float* nf, const float* g, int64_t F, float* corner, hipStream_t stream);
+
 // trace.hip -- optional per-launch event timing (sg_trace_*)
 extern std::atomic<bool> g_trace_on;
 void trace_open(int kind, int dtype, int engine, int64_t a, int64_t b, int64_t c, hipStream_t stream, int64_t* slot);

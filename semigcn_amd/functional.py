@@ -967,14 +967,75 @@ class _MeshLossScalarFn(torch.autograd.Function):
         return (grad,) + (None,) * 9
 
 
+class _MeshLossCadFn(torch.autograd.Function):
+    """_MeshLossScalarFn plus ``k2 * sum_f |n_filtered - fn|_1 / F`` (csrc/mesh_bnf.hip): the filter runs in the forward and
+    carries no gradient (util/loss.py:232); the backward's one pass over the faces takes both normal targets, then the same
+    fixed-order CSR sum.  ``target_pos`` None: the bilateral term alone.  Returns (loss, n_filtered)."""
+
+    @staticmethod
+    def forward(ctx, pos, faces, target_pos, v_keep, target_fn, f_keep, f2f, n_v, n_f, w_pos, k1, k2, loop, sigma_s):
+        pos = pos.contiguous()
+        part = None if target_pos is None else capi.mesh_loss_fwd(pos, faces, target_pos, v_keep, target_fn, f_keep)
+        fn, nf, bpart = capi.bnf_filter(pos, faces, f2f, loop, sigma_s, with_partials=True)
+        out = capi.mesh_loss_cad_finalize(part, n_v, n_f, w_pos, k1, bpart, faces.shape[0], k2)
+        ctx.with_base = target_pos is not None
+        ctx.save_for_backward(pos, faces, fn, nf, out, *((target_pos, v_keep, target_fn, f_keep) if ctx.with_base else ()))
+        ctx.mark_non_differentiable(nf)
+        return out[0], nf
+
+    @staticmethod
+    def backward(ctx, g, _g_nf):
+        pos, faces, fn, nf, out = ctx.saved_tensors[:5]
+        target_pos, v_keep, target_fn, f_keep = ctx.saved_tensors[5:] if ctx.with_base else (None,) * 4
+        grad = capi.mesh_loss_cad_bwd_det(pos, faces, target_pos, v_keep, target_fn, f_keep, fn, nf, out[1:] * g,
+                                          _face_incidence(faces, pos.shape[0]))
+        return (grad,) + (None,) * 13
+
+
+def _bnf_args(pos, faces, f2f, loop, sigma_s):
+    for t, name in ((pos, "pos"), (faces, "faces"), (f2f, "f2f")):
+        capi._require_device(t, name)
+    if pos.dtype != torch.float32:
+        raise capi.SemigcnLibraryError(f"the bilateral normal filter is float32 only, got {pos.dtype}")
+    if loop < 0 or not sigma_s > 0:
+        raise ValueError(f"bilateral normal filter: loop must be >= 0 and sigma_s > 0, got {loop}, {sigma_s}")
+    if faces.shape[0] == 0:
+        raise ValueError("bilateral normal filter: the mesh has no faces")
+
+
+def bilateral_normal_filter(pos: torch.Tensor, faces: torch.Tensor, f2f: torch.Tensor, fn: Optional[torch.Tensor] = None,
+                            loop: int = 5, sigma_s: float = 0.3) -> torch.Tensor:
+    """``Models.bnf`` (util/models.py:209-237) / the loop of ``fn_bnf_detach_loss`` (util/loss.py:219-232) as an operation:
+    ``loop`` rounds of bilateral filtering of the face normals ``fn`` [F,3] (None: the unit face normals of ``pos``) over
+    the face ring ``f2f`` ([F,3] int64, -1 = no neighbour; meshprep.MeshTopology.f2f).  No autograd: the inputs are taken
+    detached and the result carries no gradient."""
+    _bnf_args(pos, faces, f2f, loop, sigma_s)
+    start = None if fn is None else fn.detach().contiguous()
+    return capi.bnf_filter(pos.detach().contiguous(), faces, f2f, loop, sigma_s, start_fn=start)[1]
+
+
+def bilateral_normal_loss(pos: torch.Tensor, faces: torch.Tensor, f2f: torch.Tensor, loop: int = 5, sigma_s: float = 0.3):
+    """``Loss.fn_bnf_detach_loss(pos, compute_fn(pos), mesh)`` (util/loss.py:197-253, 'l1mae') -> (loss, n_filtered):
+    differentiable in ``pos`` through the face normals only, with the deterministic backward of the fused loss step."""
+    _bnf_args(pos, faces, f2f, loop, sigma_s)
+    return _MeshLossCadFn.apply(pos, faces, None, None, None, None, f2f, 1.0, 0.0, 0.0, 0.0, 1.0, int(loop), float(sigma_s))
+
+
 _no_faces: dict = {}
 
 
 def mesh_loss(pos: torch.Tensor, faces: Optional[torch.Tensor], target_pos: torch.Tensor, v_keep: torch.Tensor,
               target_fn: Optional[torch.Tensor], f_keep: Optional[torch.Tensor], n_v: float, n_f: float, w_pos: float = 1.0,
-              k1: float = 0.0) -> torch.Tensor:
+              k1: float = 0.0, *, k2: float = 0.0, f2f: Optional[torch.Tensor] = None, loop: int = 5) -> torch.Tensor:
     """The loss of sgcn.py:130-138 -- ``mask_pos_rec_loss + k1 * mask_norm_rec_loss`` on the positions the network produced --
-    as one scalar; with ``faces=None`` one resolution's weighted position term of mgcn.py:138-143 (``w_pos`` = its weight)."""
+    as one scalar; with ``faces=None`` one resolution's weighted position term of mgcn.py:138-143 (``w_pos`` = its weight).
+    ``k2 > 0`` adds ``k2 * fn_bnf_detach_loss`` (the -CAD term, sgcn.py:133-135) over the face ring ``f2f`` inside the same
+    node: one scalar, one deterministic backward.  ``k2 == 0`` is the call without the keywords."""
+    if k2 != 0:
+        if faces is None or f2f is None:
+            raise ValueError("mesh_loss: k2 != 0 (the -CAD bilateral normal term) needs faces and f2f")
+        return _MeshLossCadFn.apply(pos, faces, target_pos, v_keep.reshape(-1), target_fn, f_keep.reshape(-1), f2f, float(n_v),
+                                    float(n_f), float(w_pos), float(k1), float(k2), int(loop), 0.3)[0]
     if faces is None:
         ent = _no_faces.get(pos.device)
         if ent is None:

@@ -7,9 +7,10 @@ The losses run right after the network each iteration:
   masked position RMSE  util/loss.py:14-34     (mask_pos_rec_loss, ltype='rmse')
   masked normal L1      util/loss.py:78-107    (mask_norm_rec_loss, ltype='l1mae')
   bilateral normal term util/loss.py:196-253   (fn_bnf_detach_loss; the -CAD option, off by default)
-On the device in fp32 the first three are one fused HIP forward and two backward kernels
-(functional.mesh_loss_sums, csrc/mesh_loss.hip); the plain-torch versions below serve other
-dtypes, MGCN's coarse levels and the tests.  Unlike the reference no ``.item()`` is taken
+On the device in fp32 all four are one fused loss node (functional.mesh_loss: csrc/mesh_loss.hip,
+and csrc/mesh_bnf.hip for the -CAD term when k2 > 0) with a bit-reproducible backward; the
+plain-torch versions below serve other dtypes, the CPU and the tests.  ``fn_bnf_detach_loss`` has the
+reference's signature, for a reference script that is pointed at this module.  Unlike the reference no ``.item()`` is taken
 inside the loop (sgcn.py:140-144 forces 3-4 device syncs per iteration); loss values are
 accumulated on the device.
 """
@@ -66,6 +67,36 @@ def bilateral_normal_loss(pos: torch.Tensor, fn: torch.Tensor, faces: torch.Tens
     return (new_fn - fn).abs().sum(1).sum() / fn.shape[0], new_fn
 
 
+#: the ltypes Loss.fn_bnf_detach_loss defines (util/loss.py:234-248); the scripts only ever pass the default
+BNF_LTYPES = ("mae", "l1mae", "rmse", "l1rmse")
+
+
+def fn_bnf_detach_loss(pos, fn: torch.Tensor, mesh, ltype: str = "l1mae", loop: int = 5):
+    """Drop-in for ``Loss.fn_bnf_detach_loss(pos, fn, mesh, ltype, loop)`` (util/loss.py:197-253): returns
+    ``(loss, new_fn)`` with the gradient reaching ``fn`` only, as the reference's does.  ``mesh.faces`` / ``mesh.f2f`` may
+    be numpy arrays or tensors; ``pos`` may be a numpy array (util/loss.py:199-200).  On a HIP device in float32 the filter
+    is functional.bilateral_normal_filter (csrc/mesh_bnf.hip); elsewhere the torch composition above.  Only the 'l1mae'
+    reduction every script uses is implemented."""
+    if ltype != "l1mae":
+        if ltype in BNF_LTYPES:
+            raise NotImplementedError(f"fn_bnf_detach_loss: ltype {ltype!r} is not implemented (the reference defines "
+                                      f"{', '.join(BNF_LTYPES)}; its scripts only call 'l1mae')")
+        raise NotImplementedError(f"fn_bnf_detach_loss: unknown ltype {ltype!r} (the reference defines {', '.join(BNF_LTYPES)})")
+    pos = torch.as_tensor(pos).to(fn.device).detach()
+    faces = torch.as_tensor(mesh.faces).long().to(fn.device)
+    f2f = torch.as_tensor(mesh.f2f).long().to(fn.device)
+    if fn.is_cuda and fn.dtype == torch.float32 and pos.dtype == torch.float32:
+        from .functional import bilateral_normal_filter
+        new_fn = bilateral_normal_filter(pos, faces.contiguous(), f2f.contiguous(), fn=fn, loop=loop)
+        return (new_fn - fn).abs().sum(1).sum() / fn.shape[0], new_fn
+    return bilateral_normal_loss(pos, fn, faces, f2f, loop=loop)
+
+
+#: k2 > 0 on the device in fp32 goes through the fused loss node; False routes the trainers back onto the torch
+#: composition ``bilateral_normal_loss`` (A/B timing, and the tests that compare the two)
+FUSED_CAD_TERM = True
+
+
 @dataclass
 class MeshBatch:
     """Per-mesh constants of the training loop, resident on the device."""
@@ -78,7 +109,8 @@ class MeshBatch:
     dummy_masks: torch.Tensor    # [V, n_masks] float (vmask_dummy)
     n_v_keep: int = 0
     n_f_keep: int = 0
-    f2f: Optional[torch.Tensor] = None   # [F,3] int64 face 1-ring, -1 padded; only for the -CAD term (k2 > 0)
+    f2f: Optional[torch.Tensor] = None   # [F,3] int64 face 1-ring, -1 padded; only for the -CAD term (k2 > 0).
+    #                                      meshprep.MeshTopology(faces, V, device).f2f is the intended source
 
     def __post_init__(self):
         self.n_v_keep = int(self.v_keep.sum().item())
@@ -387,6 +419,9 @@ class SGCNTrainer(_Epochs):
         b = self.mesh
         if pos.is_cuda and pos.dtype == torch.float32:     # fused HIP kernels (csrc/mesh_loss.hip): one scalar
             from .functional import mesh_loss
+            if self.k2 > 0 and FUSED_CAD_TERM:       # the -CAD term inside the same node (csrc/mesh_bnf.hip)
+                return mesh_loss(pos, b.faces, b.target_pos, b.v_keep, b.target_fn, b.f_keep, b.n_v_keep, b.n_f_keep, 1.0, self.k1,
+                                 k2=self.k2, f2f=b.f2f)
             loss = mesh_loss(pos, b.faces, b.target_pos, b.v_keep, b.target_fn, b.f_keep, b.n_v_keep, b.n_f_keep, 1.0, self.k1)
             if self.k2 > 0:
                 loss = loss + self.k2 * bilateral_normal_loss(pos, face_normals(pos, b.faces), b.faces, b.f2f)[0]
@@ -454,17 +489,19 @@ class MGCNTrainer(_Epochs):
         if poss[0].is_cuda and poss[0].dtype == torch.float32:
             # finest level: position and normal terms from the fused HIP kernels (csrc/mesh_loss.hip), as in SGCNTrainer
             from .functional import mesh_loss
+            fused_cad = self.k2 > 0 and FUSED_CAD_TERM      # the -CAD term inside the same node (csrc/mesh_bnf.hip)
             loss = mesh_loss(poss[0], b.faces, self.model.poss_list[0], self.keeps[0], b.target_fn, b.f_keep, self.counts[0],
-                             b.n_f_keep, self.weights[0], self.k1)
+                             b.n_f_keep, self.weights[0], self.k1, k2=self.k2 if fused_cad else 0.0, f2f=b.f2f)
             fn = None
             for w, p, t, keep, n in list(zip(self.weights, poss, self.model.poss_list, self.keeps, self.counts))[1:]:
                 loss = loss + mesh_loss(p, None, t, keep, None, None, n, 0.0, w)     # the coarser resolutions: position term only
         else:
+            fused_cad = False
             fn = face_normals(poss[0], b.faces)
             loss = self.k1 * masked_normal_l1(fn, b.target_fn, b.f_keep, b.n_f_keep)
             for w, p, t, keep, n in zip(self.weights, poss, self.model.poss_list, self.keeps, self.counts):
                 loss = loss + w * masked_position_rmse(p, t, keep, n)
-        if self.k2 > 0:
+        if self.k2 > 0 and not fused_cad:
             fn = face_normals(poss[0], b.faces) if fn is None else fn
             loss = loss + self.k2 * bilateral_normal_loss(poss[0], fn, b.faces, b.f2f)[0]
         from .functional import sink_param_grads
