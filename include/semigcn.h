@@ -356,6 +356,42 @@ SG_API int sg_mesh_distance_reduce(const float* q, const float* q_org, float eps
                                    const float* gt_vs, int64_t N, uint8_t* hole_out, double* out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Network inputs from a remeshed scan -- replaces the tail of
+ * preprocess/prepare.py: edge_based_scaling (:48-52) and smooth (:110-114,
+ * pymeshlab's laplacian_smooth with stepsmoothnum=30, cotangentweight=False).
+ *
+ * sg_mean_edge_length: out[0] (device, one double) = sum ||vs[a] - vs[b]|| / E over
+ *   edges int64 [E,2] (the unique edges of sg_mesh_edges); float32 lengths summed
+ *   in float64 in a fixed order: bit-reproducible.  partial: device scratch of
+ *   sg_edge_length_blocks(E) doubles.  E == 0 gives NaN (0 / 0, as the reference);
+ *   an edge that names a vertex outside [0, V) is not read and makes the result
+ *   NaN.  Asynchronous, no host synchronisation.
+ * sg_smooth_create: the weighted neighbour lists of uniform Laplacian smoothing
+ *   with MeshLab's border rule, built once from faces int64 [F,3]:
+ *     k_ij = number of faces that use the undirected edge {i,j}; k = 1 is a border
+ *     edge; a vertex is a border vertex if any of its edges is a border edge.
+ *     interior vertex: w_ij = k_ij.  border vertex: w_ij = 1 on its border edges,
+ *     0 on all its other edges.
+ *   A face index outside [0, V), a face with a repeated vertex or an edge with
+ *   more than 255 faces gives SG_ERR_INVALID.  Synchronises the stream.
+ * sg_smooth_run: `steps` Jacobi steps p_i <- (p_i + sum_j w_ij p_j) / (1 + sum_j w_ij)
+ *   from in float32 [V,3] to out float32 [V,3] (may be the same array).  A vertex
+ *   without edges, or with movable_or_null[i] == 0 (V bytes), keeps its position
+ *   bit for bit.  steps == 0 copies.  One launch to load the plan's 16-byte
+ *   position records and one per step, ping-ponging between the plan's two
+ *   buffers; every vertex sums its own neighbour list in ascending neighbour
+ *   order: no atomics, no grid barrier, no host synchronisation, bit-reproducible.
+ *   The buffers belong to the plan: one run at a time per plan.
+ * ------------------------------------------------------------------------- */
+typedef struct sg_smooth sg_smooth;
+SG_API int64_t sg_edge_length_blocks(int64_t E);
+SG_API int sg_mean_edge_length(const float* vs, int64_t V, const int64_t* edges, int64_t E, double* partial, double* out,
+                               void* stream);
+SG_API int sg_smooth_create(const int64_t* faces, int64_t F, int64_t V, void* stream, sg_smooth** out);
+SG_API int sg_smooth_destroy(sg_smooth* s);
+SG_API int sg_smooth_run(sg_smooth* s, const float* in, float* out, const uint8_t* movable_or_null, int steps, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Loss step of the training loop, fused -- replaces Models.compute_fn
  * (util/models.py:121-126), Loss.mask_pos_rec_loss (util/loss.py:14-34, 'rmse')
  * and Loss.mask_norm_rec_loss (util/loss.py:78-107, 'l1mae') as sgcn.py:130-132

@@ -199,6 +199,11 @@ _SIGNATURES = {
     "sg_surface_query": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_mesh_distance_reduce": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                         c_void_p]),
+    "sg_edge_length_blocks": (c_int64, [c_int64]),
+    "sg_mean_edge_length": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sg_smooth_create": (c_int, [c_void_p, c_int64, c_int64, c_void_p, POINTER(c_void_p)]),
+    "sg_smooth_destroy": (c_int, [c_void_p]),
+    "sg_smooth_run": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 _lib = None
@@ -1342,6 +1347,81 @@ def mesh_distance_reduce(q: torch.Tensor, gt_vs: torch.Tensor, q_org: Optional[t
         _check(load().sg_mesh_distance_reduce(_ptr(q), _ptr(q_org), float(eps), _ptr(hole), _ptr(gt_vs), N, _ptr(hole_out),
                                               _ptr(out), _stream(q)), "sg_mesh_distance_reduce")
     return out, hole_out
+
+
+def mean_edge_length(vs: torch.Tensor, edges: torch.Tensor) -> torch.Tensor:
+    """0-dim float64 device tensor: sum ||vs[a] - vs[b]|| / E over edges int64 [E, 2] (preprocess/prepare.py:48-52); float32
+    lengths summed in float64 in a fixed order.  Two launches, no host synchronisation; E == 0 gives NaN."""
+    _require_device(vs, "vs")
+    _require_device(edges, "edges")
+    if vs.dtype != torch.float32 or vs.dim() != 2 or vs.shape[1] != 3:
+        raise SemigcnLibraryError(f"vs must be float32 [V, 3], got {vs.dtype} {tuple(vs.shape)}")
+    if edges.dtype != torch.int64 or edges.dim() != 2 or edges.shape[1] != 2:
+        raise SemigcnLibraryError(f"edges must be int64 [E, 2], got {edges.dtype} {tuple(edges.shape)}")
+    if edges.device != vs.device:
+        raise SemigcnLibraryError(f"edges on {edges.device}, vs on {vs.device}")
+    vs, edges = vs.contiguous(), edges.contiguous()
+    E = edges.shape[0]
+    part = torch.empty((_sizes("sg_edge_length_blocks", E),), dtype=torch.float64, device=vs.device)
+    out = torch.empty((), dtype=torch.float64, device=vs.device)
+    with _on_device(vs.device):
+        _check(load().sg_mean_edge_length(_ptr(vs), vs.shape[0], _ptr(edges), E, _ptr(part), _ptr(out), _stream(vs)),
+               "sg_mean_edge_length")
+    return out
+
+
+class SmoothPlan:
+    """Owns one sg_smooth: the weighted neighbour lists of uniform Laplacian smoothing with MeshLab's border rule
+    (preprocess/prepare.py:110-114; the rule is stated in semigcn_amd/prepare.py::laplacian_smooth) and the two position
+    buffers the steps ping-pong between.  One ``run`` at a time per plan."""
+
+    def __init__(self, faces: torch.Tensor, num_vertices: int):
+        _require_device(faces, "faces")
+        if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
+            raise SemigcnLibraryError(f"faces must be int64 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+        faces = faces.contiguous()
+        self.device, self.num_vertices, self.num_faces = faces.device, int(num_vertices), faces.shape[0]
+        self._h = c_void_p(0)
+        out = c_void_p()
+        with _on_device(faces.device):
+            _check(load().sg_smooth_create(_ptr(faces), faces.shape[0], self.num_vertices, _stream(faces), byref(out)),
+                   "sg_smooth_create")
+        self._h = out
+
+    def run(self, vs: torch.Tensor, steps: int = 30, movable: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """float32 [V, 3]: ``steps`` Jacobi steps from ``vs``; ``movable`` bool [V] (False = the vertex stays)."""
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError(f"steps must be >= 0, got {steps}")
+        _require_device(vs, "vs")
+        if vs.dtype != torch.float32 or tuple(vs.shape) != (self.num_vertices, 3):
+            raise SemigcnLibraryError(f"vs must be float32 [{self.num_vertices}, 3], got {vs.dtype} {tuple(vs.shape)}")
+        if vs.device != self.device:
+            raise SemigcnLibraryError(f"vs on {vs.device}, plan on {self.device}")
+        if not self._h.value:
+            raise SemigcnLibraryError("SmoothPlan is closed")
+        if movable is not None:
+            _require_device(movable, "movable")
+            if movable.numel() != self.num_vertices or movable.device != self.device:
+                raise SemigcnLibraryError(f"movable must hold {self.num_vertices} entries on {self.device}, got "
+                                          f"{tuple(movable.shape)} on {movable.device}")
+            movable = (movable.reshape(-1) != 0).contiguous()          # bool: one byte per vertex, 0 / 1
+        vs = vs.detach().contiguous()
+        out = torch.empty_like(vs)
+        with _on_device(vs.device):
+            _check(load().sg_smooth_run(self._h, _ptr(vs), _ptr(out), _ptr(movable), steps, _stream(vs)), "sg_smooth_run")
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            load().sg_smooth_destroy(self._h)
+            self._h = c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ---- one [ChebConv -> pool? -> BatchNorm -> activation] block per foreign call ---------------------------------------

@@ -530,6 +530,36 @@ SG_API int sg_mesh_distance_reduce(const float* q, const float* q_org, float eps
   return mesh_distance_reduce(q, q_org, eps, hole_in, gt_vs, N, hole_out, out, (hipStream_t)stream);
 }
 
+// preprocess/prepare.py:48-52 (edge_based_scaling) and :110-114 (smooth): csrc/mesh_smooth.hip
+SG_API int64_t sg_edge_length_blocks(int64_t E) { return E >= 0 ? edge_length_blocks(E) : -1; }
+
+SG_API int sg_mean_edge_length(const float* vs, int64_t V, const int64_t* edges, int64_t E, double* partial, double* out,
+                               void* stream) {
+  SG_REQUIRE(V >= 0 && E >= 0, "sg_mean_edge_length: negative size");
+  SG_REQUIRE(partial && out && (E == 0 || (vs && edges)), "sg_mean_edge_length: null pointer");
+  return launch_mean_edge_length(vs, V, edges, E, partial, out, (hipStream_t)stream);
+}
+
+SG_API int sg_smooth_create(const int64_t* faces, int64_t F, int64_t V, void* stream, sg_smooth** out) {
+  SG_REQUIRE(out != nullptr, "sg_smooth_create: null out");
+  *out = nullptr;
+  SG_REQUIRE(F >= 0 && V >= 0, "sg_smooth_create: negative size (F = %lld, V = %lld)", (long long)F, (long long)V);
+  SG_REQUIRE(F == 0 || faces, "sg_smooth_create: null pointer");
+  return smooth_create(faces, F, V, (hipStream_t)stream, out);
+}
+
+SG_API int sg_smooth_destroy(sg_smooth* s) {
+  destroy_smooth(s);
+  return SG_OK;
+}
+
+SG_API int sg_smooth_run(sg_smooth* s, const float* in, float* out, const uint8_t* movable_or_null, int steps, void* stream) {
+  SG_REQUIRE(steps >= 0, "sg_smooth_run: negative steps %d", steps);
+  SG_REQUIRE(s != nullptr, "sg_smooth_run: null plan");
+  SG_REQUIRE(in && out, "sg_smooth_run: null pointer");
+  return smooth_run(s, in, out, movable_or_null, steps, (hipStream_t)stream);
+}
+
 SG_API int sg_mesh_loss_bwd_det(const float* pos, const int64_t* faces, const float* target_pos, const float* v_keep,
                                 const float* target_fn, const float* f_keep, const float* g, int64_t V, int64_t V_ext,
                                 int64_t F, const sg_pool* incidence, float* corner_scratch, float* grad_pos, void* stream_) {

@@ -368,6 +368,14 @@ int launch_mesh_loss_cad_finalize(const float* partial, int64_t nb, float n_v, f
 int launch_mesh_loss_cad_bwd_corners(const float* pos, const int64_t* faces, const float* tfn, const float* fkeep, const float* fn,
                                      const float* nf, const float* g, int64_t F, float* corner, hipStream_t stream);
 
+// mesh_smooth.hip
+int64_t edge_length_blocks(int64_t E);
+int launch_mean_edge_length(const float* vs, int64_t V, const int64_t* edges, int64_t E, double* partial, double* out,
+                            hipStream_t stream);
+int smooth_create(const int64_t* faces, int64_t F, int64_t V, hipStream_t stream, sg_smooth** out);
+void destroy_smooth(sg_smooth* s);
+int smooth_run(sg_smooth* s, const float* in, float* out, const uint8_t* movable, int steps, hipStream_t stream);
+
 // trace.hip -- optional per-launch event timing (sg_trace_*)
 extern std::atomic<bool> g_trace_on;
 void trace_open(int kind, int dtype, int engine, int64_t a, int64_t b, int64_t c, hipStream_t stream, int64_t* slot);

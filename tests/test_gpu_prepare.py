@@ -1,0 +1,343 @@
+"""semigcn_amd.prepare on the device against the float64 restatement in tests/prepare_oracle.py: the smoothing rule (closed,
+open, non-manifold and isolated-vertex meshes), its reproducibility and invariants, the mean edge length, the scan mask,
+prepare_inputs -> train.MeshBatch, and the command line."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import prepare_oracle as PO
+from semigcn_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+U = 2.0 ** -24
+DEV = "cuda:0"
+
+
+# ---- meshes ------------------------------------------------------------------------------------------------------------
+def torus():
+    m = synth.torus_mesh(24, 16)
+    return m.vs.astype(np.float32), m.faces
+
+
+def sphere():
+    m = synth.octahedron_sphere(3)
+    return m.vs.astype(np.float32), m.faces
+
+
+def grid_patch(n=9, m=7, seed=3, flat_border=False):
+    """Open n x m patch, two triangles per quad (diagonals alternate), positions jittered.  ``flat_border``: the border
+    vertices keep z = 0 (the border polyline is planar)."""
+    rng = np.random.default_rng(seed)
+    i, j = np.meshgrid(np.arange(n), np.arange(m), indexing="ij")
+    vs = np.stack([i.ravel(), j.ravel(), np.zeros(n * m)], 1).astype(np.float64)
+    jit = rng.normal(0.0, 0.15, vs.shape)
+    if flat_border:
+        on = (i.ravel() == 0) | (i.ravel() == n - 1) | (j.ravel() == 0) | (j.ravel() == m - 1)
+        jit[on, 2] = 0.0
+    vs += jit
+    faces = []
+    for a in range(n - 1):
+        for b in range(m - 1):
+            v00, v10, v11, v01 = a * m + b, (a + 1) * m + b, (a + 1) * m + b + 1, a * m + b + 1
+            faces += [[v00, v10, v11], [v00, v11, v01]] if (a + b) % 2 == 0 else [[v00, v10, v01], [v10, v11, v01]]
+    return vs.astype(np.float32), np.asarray(faces, np.int64)
+
+
+def fin_mesh():
+    """The sphere with a blister over face 0 whose floor is kept: the three edges of that face carry three faces each
+    (k = 3) and the mesh has no border edge, so the weight 3 is really used."""
+    vs, faces = sphere()
+    a, b, c = faces[0]
+    top = vs[[a, b, c]].astype(np.float64).mean(0) * 1.25
+    v = vs.shape[0]
+    vs = np.concatenate([vs, top[None].astype(np.float32)])
+    faces = np.concatenate([faces, [[a, b, v], [b, c, v], [c, a, v]]])
+    return vs, faces
+
+
+def isolated_mesh():
+    vs, faces = sphere()
+    vs = np.concatenate([vs[:5], np.array([[7.0, -3.0, 2.5]], np.float32), vs[5:]])       # vertex 5 is in no face
+    faces = np.where(faces >= 5, faces + 1, faces)
+    return vs, faces
+
+
+MESHES = {"torus": torus, "sphere": sphere, "grid": grid_patch, "fin": fin_mesh, "isolated": isolated_mesh}
+
+
+def dev(x, dtype=None):
+    t = torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
+    return t if dtype is None else t.to(dtype)
+
+
+def bound(steps, d_max, vs):
+    """max |error| <= 2 steps (d_max + 3) u max|p|: one step is a convex combination of at most d_max + 1 float32 terms plus
+    one divide, (d_max + 3) u max|p|; a convex combination is non-expansive in the max norm, so the errors add across steps;
+    the factor 2 is slack for fused against unfused multiply-add."""
+    return 2.0 * steps * (d_max + 3) * U * float(np.abs(vs).max())
+
+
+# ---- smoothing ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("steps", [1, 2, 30])
+@pytest.mark.parametrize("name", list(MESHES))
+def test_smoothing_vs_float64(name, steps):
+    from semigcn_amd import prepare
+    vs, faces = MESHES[name]()
+    d_max, C = PO.neighbour_lists(faces, vs.shape[0])
+    if name == "fin":                                             # the blister's floor: two neighbours weigh 3, the others 2
+        deg = np.bincount(PO.unique_edges(faces, vs.shape[0]).ravel(), minlength=vs.shape[0])
+        assert np.array_equal(C[faces[0]], 2.0 * deg[faces[0]] + 2.0) and np.array_equal(np.delete(C, faces[0]), 2.0 * np.delete(deg, faces[0]))
+    if name == "grid":
+        assert (C == 2).sum() >= 2 * (9 + 7) - 4                  # border vertices: two border edges each
+    if name == "isolated":
+        assert C[5] == 0
+    want = PO.smooth(vs, faces, steps)
+    got = prepare.laplacian_smooth(dev(vs), dev(faces), steps=steps)
+    assert got.dtype == torch.float32 and tuple(got.shape) == vs.shape
+    err = float(np.abs(got.cpu().numpy().astype(np.float64) - want).max())
+    b = bound(steps, d_max, vs)
+    print(f"{name} steps={steps}: max|err| {err:.3e}  bound {b:.3e}  d_max {d_max}")
+    assert err <= b
+    assert float(np.abs(want - vs).max()) > 100 * b               # the step moved the mesh by far more than the bound
+    if name == "isolated":
+        assert np.array_equal(got.cpu().numpy()[5], vs[5])
+
+
+def test_zero_steps_is_a_copy_and_negative_steps_raise():
+    from semigcn_amd import prepare
+    vs, faces = torus()
+    x = dev(vs)
+    out = prepare.laplacian_smooth(x, dev(faces), steps=0)
+    assert torch.equal(out, x) and out.data_ptr() != x.data_ptr()
+    with pytest.raises(ValueError, match="steps"):
+        prepare.laplacian_smooth(x, dev(faces), steps=-1)
+
+
+@pytest.mark.parametrize("name", ["torus", "grid"])
+def test_fixed_vertices(name):
+    from semigcn_amd import prepare
+    vs, faces = MESHES[name]()
+    rng = np.random.default_rng(11)
+    movable = rng.random(vs.shape[0]) < 0.7
+    steps = 5
+    got = prepare.laplacian_smooth(dev(vs), dev(faces), steps=steps, movable=dev(movable)).cpu().numpy()
+    assert np.array_equal(got[~movable].view(np.uint32), vs[~movable].view(np.uint32))
+    want = PO.smooth(vs, faces, steps, movable)
+    d_max, _ = PO.neighbour_lists(faces, vs.shape[0])
+    err = float(np.abs(got.astype(np.float64) - want).max())
+    print(f"{name} fixed: max|err| {err:.3e}  bound {bound(steps, d_max, vs):.3e}")
+    assert err <= bound(steps, d_max, vs)
+    assert (got[movable] != vs[movable]).any()
+
+
+def test_reproducibility():
+    from semigcn_amd import prepare
+    from semigcn_amd.meshprep import MeshTopology
+    for name in ("torus", "grid", "fin"):
+        vs, faces = MESHES[name]()
+        x, f = dev(vs), dev(faces)
+        plan = prepare.SmoothPlan(f, vs.shape[0])
+        a = prepare.laplacian_smooth(x, plan, steps=30)
+        b = prepare.laplacian_smooth(x, plan, steps=30)
+        assert torch.equal(a, b)
+        c = prepare.laplacian_smooth(prepare.laplacian_smooth(x, plan, steps=12), plan, steps=18)
+        assert torch.equal(a, c)
+        d = prepare.laplacian_smooth(x, MeshTopology(f, vs.shape[0], DEV, with_f2f=False), steps=30)
+        e = prepare.laplacian_smooth(x, f, steps=30)
+        g = prepare.laplacian_smooth(vs, faces, steps=30)             # numpy in
+        assert torch.equal(a, d) and torch.equal(a, e) and torch.equal(a, g)
+        plan.close()
+        plan.close()                                                  # idempotent
+
+
+def test_closed_mesh_conserves_weighted_sum():
+    """On a closed mesh every vertex is interior and w_ij = w_ji: sum_i (1 + sum_j w_ij) p_i is conserved by a step.  The
+    device result keeps it up to the per-vertex rounding bound of one step, summed over the vertices."""
+    from semigcn_amd import prepare
+    for name in ("torus", "sphere", "fin"):
+        vs, faces = MESHES[name]()
+        d_max, C = PO.neighbour_lists(faces, vs.shape[0])
+        got = prepare.laplacian_smooth(dev(vs), dev(faces), steps=1).cpu().numpy().astype(np.float64)
+        before = ((1.0 + C)[:, None] * vs.astype(np.float64)).sum(0)
+        after = ((1.0 + C)[:, None] * got).sum(0)
+        tol = float((1.0 + C).sum()) * bound(1, d_max, vs)
+        assert np.abs(after - before).max() <= tol
+        assert np.abs(after - before).max() <= 1e-4 * np.abs((1.0 + C)[:, None] * vs).sum(0).max()
+
+
+def test_border_vertices_stay_in_the_border_plane():
+    """A border vertex reads border neighbours only: with the border polyline in the plane z = 0 it never leaves that plane,
+    whatever the (jittered) interior does."""
+    from semigcn_amd import prepare
+    n, m = 9, 7
+    vs, faces = grid_patch(n, m, flat_border=True)
+    got = prepare.laplacian_smooth(dev(vs), dev(faces), steps=30).cpu().numpy()
+    i, j = np.meshgrid(np.arange(n), np.arange(m), indexing="ij")
+    i, j = i.ravel(), j.ravel()
+    on = (i == 0) | (i == n - 1) | (j == 0) | (j == m - 1)
+    assert np.array_equal(got[on, 2], np.zeros(on.sum(), np.float32))          # the border polyline's plane, exactly
+    assert np.abs(got[~on, 2]).max() > 0                                        # the interior is not flat
+
+
+# ---- mean edge length --------------------------------------------------------------------------------------------------
+def test_mean_edge_length():
+    from semigcn_amd import prepare
+    from semigcn_amd.meshprep import MeshTopology
+    for name in ("torus", "sphere", "grid", "fin"):
+        vs, faces = MESHES[name]()
+        topo = MeshTopology(dev(faces), vs.shape[0], DEV, with_f2f=False)
+        edges = topo.edges
+        assert edges.shape[0] == PO.unique_edges(faces, vs.shape[0]).shape[0]
+        got = prepare.mean_edge_length(dev(vs), edges)
+        assert got.dtype == torch.float64 and got.dim() == 0 and got.is_cuda
+        want = PO.mean_edge_length(vs, edges.cpu().numpy())
+        rel = abs(float(got) - want) / want
+        print(f"{name}: mean edge {float(got)!r} oracle {want!r} rel {rel:.3e}")
+        assert rel <= 8 * U
+        assert float(got) == float(prepare.mean_edge_length(dev(vs), edges))
+    # more edges than one block holds, and more blocks than the reduction's cap
+    m = synth.torus_mesh(400, 300, masks=False)
+    vs = m.vs.astype(np.float32)
+    got = prepare.mean_edge_length(dev(vs), dev(m.edges))
+    want = PO.mean_edge_length(vs, m.edges)
+    assert abs(float(got) - want) / want <= 8 * U
+    assert torch.equal(got, prepare.mean_edge_length(dev(vs), dev(m.edges)))
+    empty = prepare.mean_edge_length(dev(vs), torch.zeros((0, 2), dtype=torch.int64, device=DEV))
+    assert bool(torch.isnan(empty))
+
+
+# ---- scan mask ---------------------------------------------------------------------------------------------------------
+def holed_torus(nu=48, nv=24, rings=5):
+    """(vs float32, faces, faces of `original`, inner): a torus of unit mean edge length; `original` is the same mesh without
+    the faces that touch a vertex closer than ``rings`` rings to a vertex on the outer equator; ``inner`` marks those
+    vertices (they lie in no face of `original`; the rim of the hole, ring ``rings``, still does)."""
+    m = synth.torus_mesh(nu, nv, masks=False)
+    V = m.num_vertices
+    centre = (nu // 2) * nv
+    AI = synth.adjacency_plus_identity(m.edge_index, V)
+    reach = np.zeros((V, 1), np.float32)
+    reach[centre] = 1
+    for _ in range(rings - 1):
+        reach = (AI @ reach > 0).astype(np.float32)
+    inner = reach[:, 0] > 0
+    keep = ~inner[m.faces].any(1)
+    vs = m.vs / PO.mean_edge_length(m.vs, m.edges)
+    return vs.astype(np.float32), m.faces, m.faces[keep], inner
+
+
+def test_scan_mask_equals_oracle():
+    from semigcn_amd import prepare
+    from semigcn_amd.evaluate import Surface
+    vs, faces, org_faces, inner = holed_torus()
+    assert 30 < inner.sum() < 120
+    dist = PO.scan_distances(vs, vs, org_faces)
+    assert not ((dist >= 0.1) & (dist <= 0.3)).any()              # the premise: no distance anywhere near eps = 0.2
+    want = dist < 0.2
+    assert np.array_equal(want, ~inner)                           # on the scan everywhere but strictly inside the disc
+    assert dist[inner].min() > 0.5 and dist[~inner].max() < 1e-6
+    got = prepare.scan_mask(dev(vs), (dev(vs), dev(org_faces)))
+    assert got.dtype == torch.bool and tuple(got.shape) == (vs.shape[0],)
+    assert np.array_equal(got.cpu().numpy(), want)
+    surf = Surface(vs, org_faces)                                 # a Surface and numpy inputs as well
+    assert np.array_equal(prepare.scan_mask(vs, surf).cpu().numpy(), want)
+    assert np.array_equal(prepare.scan_mask(vs, surf, eps=0.0).cpu().numpy(), np.zeros_like(want))
+    surf.close()
+
+
+# ---- prepare_inputs ----------------------------------------------------------------------------------------------------
+def test_prepare_inputs_and_mesh_batch():
+    from semigcn_amd import meshprep, prepare, train
+    from semigcn_amd.networks import SingleScaleGCN
+    vs, faces, org_faces, inner = holed_torus(40, 20, rings=4)
+    vs = (vs * np.float32(2.75))                                  # not unit scale: the rescaling has work to do
+    p = prepare.prepare_inputs((vs, faces), (vs, org_faces), gt=(vs, faces))
+    edges = p.topology.edges.cpu().numpy()
+    want_scale = PO.mean_edge_length(vs, edges)
+    assert abs(float(p.scale) - want_scale) / want_scale <= 8 * U
+    unit = PO.mean_edge_length(p.initial_vs.cpu().numpy(), edges)
+    print(f"scale {float(p.scale)!r} oracle {want_scale!r}; mean edge after rescaling {unit!r}")
+    assert abs(unit - 1.0) <= 8 * U
+    assert abs(float(prepare.mean_edge_length(p.initial_vs, p.topology.edges)) - 1.0) <= 16 * U
+    assert torch.equal(p.initial_vs, p.original_vs) and torch.equal(p.initial_vs, p.gt_vs)
+    assert p.topology.f2f is not None and torch.equal(p.faces, dev(faces))
+    assert np.array_equal(p.v_mask.cpu().numpy(), ~inner)
+    assert torch.equal(p.f_mask, meshprep.vmask_to_fmask(p.topology, p.v_mask))
+    assert np.array_equal(p.f_mask.cpu().numpy(), (~inner)[faces].all(1))
+    assert torch.equal(p.x_pos, prepare.laplacian_smooth(p.initial_vs, p.faces, steps=30))
+    back = (p.z1 + p.x_pos - p.initial_vs).abs().max()
+    assert float(back) <= 2 * U * float(p.initial_vs.abs().max())
+    assert torch.equal(p.inserted, p.initial_vs[~p.v_mask]) and p.inserted.shape[0] == int(inner.sum())
+    q = prepare.prepare_inputs((vs, faces), (vs, org_faces), rescale=False, steps=3)
+    assert float(q.scale) == 1.0 and q.gt_vs is None and torch.equal(q.initial_vs, dev(vs)) and q.steps == 3
+
+    def first_loss(batch, k2=0.0, iters=1):
+        torch.manual_seed(7)
+        net = SingleScaleGCN(DEV).to(DEV)
+        tr = train.SGCNTrainer(net, batch, k2=k2)
+        return [float(tr.iteration_step(k % batch.dummy_masks.shape[1])) for k in range(iters)]
+
+    batch = p.mesh_batch(dm_size=4, kn=(2,), rng=np.random.RandomState(9))
+    V, F = vs.shape[0], faces.shape[0]
+    assert tuple(batch.dummy_masks.shape) == (V, 4) and tuple(batch.v_keep.shape) == (V, 1) and tuple(batch.f_keep.shape) == (F, 1)
+    assert batch.n_v_keep == int((~inner).sum()) and batch.n_f_keep == int(p.f_mask.sum())
+    assert batch.data.z1.requires_grad and torch.equal(batch.data.z1.detach(), p.z1) and batch.data.x_pos is p.x_pos
+    assert torch.equal(batch.data.edge_index, p.topology.edge_index) and batch.f2f is p.topology.f2f
+
+    class Data:
+        z1 = p.z1.clone().requires_grad_(True)
+        x_pos = p.x_pos
+        edge_index = p.topology.edge_index
+    dm = meshprep.make_dummy_mask(p.topology, dm_size=4, kn=(2,), rng=np.random.RandomState(9))[0]
+    hand = train.MeshBatch(Data, p.faces, p.initial_vs, train.face_normals(p.initial_vs, p.faces), p.v_mask.float().view(-1, 1),
+                           p.f_mask.float().view(-1, 1), dm, f2f=p.topology.f2f)
+    assert torch.equal(batch.dummy_masks, hand.dummy_masks)
+    a, b = first_loss(batch), first_loss(hand)
+    assert a == b and np.isfinite(a[0])
+    cad = first_loss(p.mesh_batch(dm_size=4, kn=(2,), rng=np.random.RandomState(9)), k2=4.0, iters=3)
+    assert np.isfinite(cad).all() and cad[0] > a[0]
+
+
+# ---- command line ------------------------------------------------------------------------------------------------------
+def test_command_line(tmp_path):
+    from semigcn_amd import prepare
+    from semigcn_amd.evaluate import read_obj
+    vs, faces, org_faces, inner = holed_torus(40, 20, rings=4)
+    vs = vs * np.float32(1.5)
+    src, out = tmp_path / "in", tmp_path / "out"
+    src.mkdir()
+    prepare.write_obj(str(src / "A_initial.obj"), vs, faces)
+    prepare.write_obj(str(src / "A_original.obj"), vs, org_faces)
+    prepare.write_obj(str(src / "A_gt.obj"), vs, faces)
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([sys.executable, "-m", "semigcn_amd.prepare", "--initial", str(src / "A_initial.obj"), "--original",
+                        str(src / "A_original.obj"), "--gt", str(src / "A_gt.obj"), "--out-dir", str(out)],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    for tail in ("_initial.obj", "_original.obj", "_gt.obj", "_smooth.obj", "_vmask.json", "_inserted.obj"):
+        assert (out / ("A" + tail)).is_file(), tail
+    info = json.loads(r.stdout.strip().splitlines()[-1])
+    assert set(info) == {"scale", "n_vertices", "n_masked", "steps"}
+    assert info["n_vertices"] == vs.shape[0] and info["n_masked"] == int((~inner).sum()) and info["steps"] == 30
+    ini_vs, ini_f = read_obj(str(out / "A_initial.obj"))
+    org_vs, org_f = read_obj(str(out / "A_original.obj"))
+    gt_vs, _ = read_obj(str(out / "A_gt.obj"))
+    assert np.array_equal(ini_f, faces) and np.array_equal(org_f, org_faces) and np.array_equal(gt_vs, ini_vs)
+    edges = PO.unique_edges(faces, vs.shape[0])
+    assert abs(info["scale"] - PO.mean_edge_length(vs, edges)) / info["scale"] <= 8 * U
+    assert np.array_equal(ini_vs, (vs.astype(np.float64) / info["scale"]).astype(np.float32))
+    mask = json.load(open(out / "A_vmask.json"))
+    assert len(mask) == vs.shape[0] and all(isinstance(b, bool) for b in mask)
+    assert np.array_equal(np.asarray(mask), prepare.scan_mask(ini_vs, (org_vs, org_f)).cpu().numpy())
+    assert np.array_equal(np.asarray(mask), ~inner)
+    sm_vs, sm_f = read_obj(str(out / "A_smooth.obj"))
+    want = prepare.laplacian_smooth(ini_vs, ini_f, steps=30).cpu().numpy()
+    assert np.array_equal(sm_f, faces) and np.array_equal(sm_vs.view(np.uint32), want.view(np.uint32))
+    ins_vs, ins_f = read_obj(str(out / "A_inserted.obj"))
+    assert ins_f.shape[0] == 0 and np.array_equal(ins_vs, ini_vs[~np.asarray(mask)])
