@@ -392,6 +392,43 @@ SG_API int sg_smooth_destroy(sg_smooth* s);
 SG_API int sg_smooth_run(sg_smooth* s, const float* in, float* out, const uint8_t* movable_or_null, int steps, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Hole filling -- replaces the hole-closing part of MeshFix.repair()
+ * (preprocess/prepare.py:28-33): boundary loops of a triangle list and a ring
+ * patch for every loop.  The construction (ring counts, vertex positions, face
+ * order) is specified in semigcn_amd/holes.py.
+ *
+ * sg_fill_create: finds the boundary half-edges of faces int64 [F,3] (a directed
+ *   half-edge (a,b) without its opposite (b,a)) and orders them into loops by
+ *   pointer jumping.  Loops are numbered by ascending smallest vertex, start at
+ *   it and run AGAINST the mesh's half-edges.  A face index outside [0, V) or a
+ *   face with a repeated vertex gives SG_ERR_INVALID.  A repeated directed
+ *   half-edge, or a vertex with more than one outgoing boundary half-edge,
+ *   makes the boundary unorderable: the plan is still returned, sg_fill_query
+ *   reports the counts, and sg_fill_loops / sg_fill_plan / sg_fill_emit fail.
+ *   Synchronises the stream.
+ * sg_fill_query: info[8] (host) = number of loops, number of boundary
+ *   half-edges, repeated directed half-edges, vertices with more than one
+ *   outgoing boundary half-edge, the smallest offending vertex (-1: none), new
+ *   vertices and new faces of the last sg_fill_plan (-1: none yet), V.
+ * sg_fill_loops: copies loop_ptr int64 [L+1] and loop_verts int64 [info[1]] to
+ *   device arrays of the caller.
+ * sg_fill_plan: sizes the patches of every loop of at most max_hole_edges edges
+ *   (negative: every loop) and returns the number of new vertices and faces.
+ *   Synchronises the stream.
+ * sg_fill_emit: writes the new vertices float32 [Vn,3], the new faces int64
+ *   [Fn,3] (new vertex g has the id V + g) and filled uint8 [L], in loop order,
+ *   then ring order, then index order, from the positions vs float32 [V,3].
+ *   Asynchronous; the arc lengths live in the plan: one emit at a time per plan.
+ * ------------------------------------------------------------------------- */
+typedef struct sg_fill sg_fill;
+SG_API int sg_fill_create(const int64_t* faces, int64_t F, int64_t V, void* stream, sg_fill** out);
+SG_API int sg_fill_destroy(sg_fill* s);
+SG_API int sg_fill_query(const sg_fill* s, int64_t* info);
+SG_API int sg_fill_loops(const sg_fill* s, int64_t* loop_ptr_out, int64_t* loop_verts_out, void* stream);
+SG_API int sg_fill_plan(sg_fill* s, int64_t max_hole_edges, void* stream, int64_t* n_new_vertices, int64_t* n_new_faces);
+SG_API int sg_fill_emit(sg_fill* s, const float* vs, float* new_vs, int64_t* new_faces, uint8_t* filled_out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Loss step of the training loop, fused -- replaces Models.compute_fn
  * (util/models.py:121-126), Loss.mask_pos_rec_loss (util/loss.py:14-34, 'rmse')
  * and Loss.mask_norm_rec_loss (util/loss.py:78-107, 'l1mae') as sgcn.py:130-132

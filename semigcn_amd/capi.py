@@ -204,6 +204,12 @@ _SIGNATURES = {
     "sg_smooth_create": (c_int, [c_void_p, c_int64, c_int64, c_void_p, POINTER(c_void_p)]),
     "sg_smooth_destroy": (c_int, [c_void_p]),
     "sg_smooth_run": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "sg_fill_create": (c_int, [c_void_p, c_int64, c_int64, c_void_p, POINTER(c_void_p)]),
+    "sg_fill_destroy": (c_int, [c_void_p]),
+    "sg_fill_query": (c_int, [c_void_p, POINTER(c_int64)]),
+    "sg_fill_loops": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_fill_plan": (c_int, [c_void_p, c_int64, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    "sg_fill_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -1422,6 +1428,98 @@ class SmoothPlan:
             self.close()
         except Exception:
             pass
+
+
+class FillPlan:
+    """Owns one sg_fill (csrc/mesh_fill.hip): the boundary loops of a triangle list and, after ``plan``, the sizes of the
+    patches that close them (the construction is specified in semigcn_amd/holes.py).  ``n_repeated`` / ``n_bowtie`` /
+    ``bad_vertex`` say why a boundary cannot be ordered; ``loops`` / ``plan`` / ``emit`` then raise."""
+
+    def __init__(self, faces: torch.Tensor, num_vertices: int):
+        _require_device(faces, "faces")
+        if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
+            raise SemigcnLibraryError(f"faces must be int64 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+        faces = faces.contiguous()
+        self.device, self.num_vertices, self.num_faces = faces.device, int(num_vertices), faces.shape[0]
+        self._h = c_void_p(0)
+        out = c_void_p()
+        with _on_device(faces.device):
+            _check(load().sg_fill_create(_ptr(faces), faces.shape[0], self.num_vertices, _stream(faces), byref(out)),
+                   "sg_fill_create")
+        self._h = out
+        info = self._query()
+        self.num_loops, self.num_boundary, self.n_repeated, self.n_bowtie, self.bad_vertex = (int(v) for v in info[:5])
+        self.num_new_vertices = self.num_new_faces = None
+
+    def _query(self):
+        info = (c_int64 * 8)()
+        _check(load().sg_fill_query(self._h, info), "sg_fill_query")
+        return list(info)
+
+    @property
+    def orderable(self) -> bool:
+        return self.n_repeated == 0 and self.n_bowtie == 0
+
+    def _open(self):
+        if not self._h.value:
+            raise SemigcnLibraryError("FillPlan is closed")
+
+    def loops(self):
+        """(loop_ptr int64 [L + 1], loop_verts int64 [sum n]) on the plan's device."""
+        self._open()
+        ptr = torch.empty(self.num_loops + 1, dtype=torch.int64, device=self.device)
+        verts = torch.empty(max(self.num_boundary, 1), dtype=torch.int64, device=self.device)
+        with _on_device(self.device):
+            _check(load().sg_fill_loops(self._h, _ptr(ptr), _ptr(verts), _stream(ptr)), "sg_fill_loops")
+        return ptr, verts[: self.num_boundary]
+
+    def plan(self, max_hole_edges: Optional[int] = None):
+        """(new vertices, new faces) when every loop of at most ``max_hole_edges`` edges (None: every loop) is filled."""
+        self._open()
+        nv, nf = c_int64(), c_int64()
+        with _on_device(self.device):
+            _check(load().sg_fill_plan(self._h, -1 if max_hole_edges is None else int(max_hole_edges),
+                                       _raw_stream_of(self.device), byref(nv), byref(nf)), "sg_fill_plan")
+        self.num_new_vertices, self.num_new_faces = int(nv.value), int(nf.value)
+        return self.num_new_vertices, self.num_new_faces
+
+    def emit(self, vs: torch.Tensor, new_vs: torch.Tensor, new_faces: torch.Tensor) -> torch.Tensor:
+        """Writes the planned patches into ``new_vs`` float32 [Vn, 3] and ``new_faces`` int64 [Fn, 3] (contiguous, on the
+        plan's device; new vertex g has the id V + g); returns ``filled`` bool [L]."""
+        self._open()
+        if self.num_new_vertices is None:
+            raise SemigcnLibraryError("FillPlan.emit: call plan() first")
+        for t, name in ((vs, "vs"), (new_vs, "new_vs"), (new_faces, "new_faces")):
+            _require_device(t, name)
+            if t.device != self.device or not t.is_contiguous():
+                raise SemigcnLibraryError(f"{name}: a contiguous tensor on {self.device}")
+        if vs.dtype != torch.float32 or tuple(vs.shape) != (self.num_vertices, 3):
+            raise SemigcnLibraryError(f"vs must be float32 [{self.num_vertices}, 3], got {vs.dtype} {tuple(vs.shape)}")
+        if new_vs.dtype != torch.float32 or tuple(new_vs.shape) != (self.num_new_vertices, 3):
+            raise SemigcnLibraryError(f"new_vs must be float32 [{self.num_new_vertices}, 3], got {new_vs.dtype} {tuple(new_vs.shape)}")
+        if new_faces.dtype != torch.int64 or tuple(new_faces.shape) != (self.num_new_faces, 3):
+            raise SemigcnLibraryError(f"new_faces must be int64 [{self.num_new_faces}, 3], got {new_faces.dtype} "
+                                      f"{tuple(new_faces.shape)}")
+        filled = torch.zeros(max(self.num_loops, 1), dtype=torch.bool, device=self.device)
+        with _on_device(self.device):
+            _check(load().sg_fill_emit(self._h, _ptr(vs), _ptr(new_vs), _ptr(new_faces), _ptr(filled), _stream(vs)),
+                   "sg_fill_emit")
+        return filled[: self.num_loops]
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            load().sg_fill_destroy(self._h)
+            self._h = c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _raw_stream_of(device: torch.device) -> int:
+    return torch.cuda.current_stream(device).cuda_stream
 
 
 # ---- one [ChebConv -> pool? -> BatchNorm -> activation] block per foreign call ---------------------------------------

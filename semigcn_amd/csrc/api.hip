@@ -560,6 +560,45 @@ SG_API int sg_smooth_run(sg_smooth* s, const float* in, float* out, const uint8_
   return smooth_run(s, in, out, movable_or_null, steps, (hipStream_t)stream);
 }
 
+// the hole-closing part of MeshFix.repair() (preprocess/prepare.py:28-33): csrc/mesh_fill.hip
+SG_API int sg_fill_create(const int64_t* faces, int64_t F, int64_t V, void* stream, sg_fill** out) {
+  SG_REQUIRE(out != nullptr, "sg_fill_create: null out");
+  *out = nullptr;
+  SG_REQUIRE(F >= 0 && V >= 0, "sg_fill_create: negative size (F = %lld, V = %lld)", (long long)F, (long long)V);
+  SG_REQUIRE(F == 0 || faces, "sg_fill_create: null pointer");
+  return fill_create(faces, F, V, (hipStream_t)stream, out);
+}
+
+SG_API int sg_fill_destroy(sg_fill* s) {
+  destroy_fill(s);
+  return SG_OK;
+}
+
+SG_API int sg_fill_query(const sg_fill* s, int64_t* info) {
+  SG_REQUIRE(s != nullptr, "sg_fill_query: null plan");
+  SG_REQUIRE(info != nullptr, "sg_fill_query: null pointer");
+  fill_query(s, info);
+  return SG_OK;
+}
+
+SG_API int sg_fill_loops(const sg_fill* s, int64_t* loop_ptr_out, int64_t* loop_verts_out, void* stream) {
+  SG_REQUIRE(s != nullptr, "sg_fill_loops: null plan");
+  SG_REQUIRE(loop_ptr_out && loop_verts_out, "sg_fill_loops: null pointer");
+  return fill_loops(s, loop_ptr_out, loop_verts_out, (hipStream_t)stream);
+}
+
+SG_API int sg_fill_plan(sg_fill* s, int64_t max_hole_edges, void* stream, int64_t* n_new_vertices, int64_t* n_new_faces) {
+  SG_REQUIRE(s != nullptr, "sg_fill_plan: null plan");
+  SG_REQUIRE(n_new_vertices && n_new_faces, "sg_fill_plan: null pointer");
+  return fill_plan(s, max_hole_edges, (hipStream_t)stream, n_new_vertices, n_new_faces);
+}
+
+SG_API int sg_fill_emit(sg_fill* s, const float* vs, float* new_vs, int64_t* new_faces, uint8_t* filled_out, void* stream) {
+  SG_REQUIRE(s != nullptr, "sg_fill_emit: null plan");
+  SG_REQUIRE(vs != nullptr, "sg_fill_emit: null pointer");
+  return fill_emit(s, vs, new_vs, new_faces, filled_out, (hipStream_t)stream);
+}
+
 SG_API int sg_mesh_loss_bwd_det(const float* pos, const int64_t* faces, const float* target_pos, const float* v_keep,
                                 const float* target_fn, const float* f_keep, const float* g, int64_t V, int64_t V_ext,
                                 int64_t F, const sg_pool* incidence, float* corner_scratch, float* grad_pos, void* stream_) {

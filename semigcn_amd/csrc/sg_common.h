@@ -375,6 +375,13 @@ int launch_mean_edge_length(const float* vs, int64_t V, const int64_t* edges, in
 int smooth_create(const int64_t* faces, int64_t F, int64_t V, hipStream_t stream, sg_smooth** out);
 void destroy_smooth(sg_smooth* s);
 int smooth_run(sg_smooth* s, const float* in, float* out, const uint8_t* movable, int steps, hipStream_t stream);
+// mesh_fill.hip
+int fill_create(const int64_t* faces, int64_t F, int64_t V, hipStream_t stream, sg_fill** out);
+void destroy_fill(sg_fill* s);
+void fill_query(const sg_fill* s, int64_t* info);
+int fill_loops(const sg_fill* s, int64_t* loop_ptr_out, int64_t* loop_verts_out, hipStream_t stream);
+int fill_plan(sg_fill* s, int64_t max_hole_edges, hipStream_t stream, int64_t* n_new_vertices, int64_t* n_new_faces);
+int fill_emit(sg_fill* s, const float* vs, float* new_vs, int64_t* new_faces, uint8_t* filled_out, hipStream_t stream);
 
 // trace.hip -- optional per-launch event timing (sg_trace_*)
 extern std::atomic<bool> g_trace_on;

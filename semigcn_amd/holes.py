@@ -1,0 +1,247 @@
+"""Close the holes of a scan on the device: boundary loops, one ring patch per loop, fairing of the inserted vertices.
+
+Replaces the hole-closing part of ``MeshFix.repair()`` in the reference's preprocess/prepare.py:28-33 -- the step that
+creates the vertices the network exists to place.  NOT replaced: MeshFix's other repairs (self-intersections, keeping the
+largest component) and the isotropic remesh of the whole surface that follows (preprocess/prepare.py:35-42).  MeshFix is
+not available to compare against; the construction below is this module's own and is the specification the tests pin
+(tests/holes_oracle.py restates it in numpy / float64).  The kernels are csrc/mesh_fill.hip; the fairing is
+``prepare.laplacian_smooth`` (csrc/mesh_smooth.hip) with only the inserted vertices movable.
+
+**Boundary.**  A directed half-edge ``(a, b)`` of a face (``(f0, f1)``, ``(f1, f2)``, ``(f2, f0)``) whose opposite
+``(b, a)`` belongs to no face is a boundary half-edge.  The boundary is *unorderable*, and ``ValueError`` is raised, when
+a directed half-edge occurs more than once or a vertex has more than one outgoing boundary half-edge (a "bow-tie").
+
+**Loops.**  Otherwise ``next[b] = a`` is a permutation of the boundary vertices; its cycles are the loops.  Canonical
+form: loops are numbered by ascending smallest vertex, each starts at its smallest vertex, and each runs AGAINST the
+mesh's boundary half-edges (the mesh has ``(a, b)``: the loop lists ``b`` then ``a``), so that a patch face
+``(loop[i], loop[i + 1], x)`` is oriented like the mesh.  ``ptr`` int64 [L + 1] and ``verts`` int64 [sum n] hold them.
+
+**Patch of a loop of n edges** -- topology in integer arithmetic only (``/`` below is floor division):
+
+* ``n = 3``: the one face ``(loop[0], loop[1], loop[2])``, no new vertex.
+* otherwise ``R = max(1, (113 n + 355) / 710)`` rings (``n / 2 pi`` rounded: the rings are about one border edge apart
+  on a round hole).  Ring 0 is the loop; ring ``r``, ``0 < r < R``, has ``n_r = max(3, (2 n (R - r) + R) / (2 R))``
+  vertices (``n (R - r) / R`` rounded); ring ``R`` is one vertex.
+* Vertex ``j`` of ring ``r < R`` is ``B(s) + (r / R) (c - B(s))`` with ``s = j / n_r * perimeter``: ``B`` is the loop's
+  closed polyline parameterised by arc length from ``loop[0]`` (float64 segment lengths and prefix sums in loop order,
+  ``B(s)`` on the segment ``i`` with ``cum[i] <= s < cum[i + 1]``), ``c`` the mean of the loop's vertices.  Ring ``R`` is
+  ``c``.  Computed in float64 from the float32 positions and rounded to float32 once.
+* The strip between ring ``r`` (``m`` vertices ``o``) and ring ``r + 1`` (``k > 1`` vertices ``i``) has ``m + k``
+  faces; with ``A = t m / (m + k)``, ``A' = (t + 1) m / (m + k)`` and ``B = t - A``, face ``t`` is
+  ``(o[A % m], o[(A + 1) % m], i[B % k])`` when ``A' > A`` (the outer ring advances) and
+  ``(o[A % m], i[(B + 1) % k], i[B % k])`` otherwise.  The last strip is the fan ``(o[t], o[(t + 1) % m], centre)``.
+* New vertices and faces follow the originals in loop order, then ring order, then index order.
+
+On a regular planar n-gon of edge length h (n = 4 ... 333) the unfaired patch is a closed disc with edges between
+0.707 h and 2.236 h.  An irregular loop can give much longer edges (25 h at a 30 % radial wobble, n = 1000), which is why
+the inserted vertices are faired by default.  The patch is the network's starting point, not a minimal surface.
+
+Inputs are what ``evaluate`` accepts; HIP device only: a CPU tensor raises ``SemigcnLibraryError``.
+
+Command line::
+
+    python -m semigcn_amd.holes --scan A.obj --out A_filled.obj [--max-hole-edges N] [--fair-steps K]
+    python -m semigcn_amd.holes --torus NU NV --cut K [--out A_filled.obj]
+
+prints one JSON line with ``n_loops``, ``n_filled``, ``n_inserted_vertices``, ``n_inserted_faces`` and the device time of
+each stage (``loops_ms``, ``emit_ms``, ``fair_ms``).  ``--torus NU NV --cut K`` runs on ``synth.torus_mesh(NU, NV)``
+with K discs removed, sized as ``synth.make_v_mask`` sizes its holes (5 % of the vertices in all).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import sys
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import capi, prepare
+from .capi import FillPlan, SemigcnLibraryError
+from .evaluate import _device_tensor, _vs_faces, read_obj
+
+__all__ = ["boundary_loops", "fill_holes", "BoundaryLoops", "Filled", "FillPlan"]
+
+
+@dataclass
+class BoundaryLoops:
+    """The boundary loops of a mesh in canonical form (module docstring), on the device."""
+    ptr: torch.Tensor          # int64 [L + 1]
+    verts: torch.Tensor        # int64 [sum n]
+    sizes: torch.Tensor        # int64 [L], edges (= vertices) per loop
+
+    def __len__(self) -> int:
+        return int(self.sizes.shape[0])
+
+
+@dataclass
+class Filled:
+    """What ``fill_holes`` returns.  The original vertices and faces are the prefix of ``vs`` / ``faces``, bit-identical."""
+    vs: torch.Tensor                  # float32 [V + Vn, 3]
+    faces: torch.Tensor               # int64 [F + Fn, 3]
+    num_original_vertices: int
+    num_original_faces: int
+    inserted: torch.Tensor            # bool [V + Vn], True = a vertex of a patch
+    loops: BoundaryLoops
+    filled: torch.Tensor              # bool [L], False = left open (more than max_hole_edges edges)
+    stage_ms: Optional[dict] = None   # device time of the stages, when asked for
+
+
+def _plan(faces: torch.Tensor, num_vertices: int) -> FillPlan:
+    plan = FillPlan(faces, int(num_vertices))
+    if not plan.orderable:
+        msg = (f"the boundary cannot be ordered into loops: {plan.n_repeated} directed half-edge(s) occur more than once, "
+               f"{plan.n_bowtie} vertex/vertices have more than one outgoing boundary half-edge; smallest offending "
+               f"vertex {plan.bad_vertex}")
+        plan.close()
+        raise ValueError(msg)
+    return plan
+
+
+def _loops_of(plan: FillPlan) -> BoundaryLoops:
+    ptr, verts = plan.loops()
+    return BoundaryLoops(ptr, verts, ptr[1:] - ptr[:-1])
+
+
+def boundary_loops(faces, num_vertices: int) -> BoundaryLoops:
+    """The boundary loops of the triangle list ``faces`` [F, 3] over ``num_vertices`` vertices.  ``ValueError`` when the
+    boundary is unorderable; the message names the number of repeated directed half-edges, the number of vertices with
+    more than one outgoing boundary half-edge and the smallest offending vertex."""
+    f = _device_tensor(faces, torch.int64, "faces").reshape(-1, 3)
+    plan = _plan(f, num_vertices)
+    try:
+        return _loops_of(plan)
+    finally:
+        torch.cuda.current_stream(f.device).synchronize()
+        plan.close()
+
+
+class _Stages:
+    """Device time of named stages, from events on the current stream."""
+
+    def __init__(self, device, on: bool):
+        self.on, self.device, self.marks = on, device, []
+        self.mark(None)
+
+    def mark(self, name):
+        if self.on:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record(torch.cuda.current_stream(self.device))
+            self.marks.append((name, e))
+
+    def result(self):
+        if not self.on:
+            return None
+        torch.cuda.synchronize(self.device)
+        return {name + "_ms": self.marks[i - 1][1].elapsed_time(e) for i, (name, e) in enumerate(self.marks) if i > 0}
+
+
+def fill_holes(mesh, max_hole_edges: Optional[int] = None, fair_steps: int = prepare.SMOOTH_ITER,
+               timings: bool = False) -> Filled:
+    """Close every boundary loop of ``mesh`` with at most ``max_hole_edges`` edges (``None``: every loop, as
+    ``MeshFix.repair()`` does; a cap leaves e.g. the outer border of an open scan open) by the patch of the module
+    docstring, then run ``fair_steps`` steps of ``prepare.laplacian_smooth`` with only the inserted vertices movable
+    (``0``: the raw construction).  ``ValueError`` when the boundary is unorderable; nothing is partially filled.
+    ``(Filled.vs, Filled.faces)`` is a valid ``initial`` for ``prepare.prepare_inputs``.  ``timings``: also measure the
+    device time of the stages (``Filled.stage_ms``; one more synchronisation)."""
+    fair_steps = int(fair_steps)
+    if fair_steps < 0:
+        raise ValueError(f"fill_holes: fair_steps must be >= 0, got {fair_steps}")
+    if max_hole_edges is not None and int(max_hole_edges) < 0:
+        raise ValueError(f"fill_holes: max_hole_edges must be >= 0 or None, got {max_hole_edges}")
+    vs, faces = _vs_faces(mesh)
+    V, F = vs.shape[0], faces.shape[0]
+    with capi._on_device(vs.device):
+        st = _Stages(vs.device, timings)
+        plan = _plan(faces, V)
+        try:
+            loops = _loops_of(plan)
+            st.mark("loops")
+            Vn, Fn = plan.plan(max_hole_edges)
+            out_vs = torch.empty((V + Vn, 3), dtype=torch.float32, device=vs.device)
+            out_faces = torch.empty((F + Fn, 3), dtype=torch.int64, device=vs.device)
+            out_vs[:V].copy_(vs)
+            out_faces[:F].copy_(faces)
+            filled = plan.emit(vs, out_vs[V:], out_faces[F:])
+            st.mark("emit")
+        finally:
+            torch.cuda.current_stream(vs.device).synchronize()     # the plan's buffers are freed with it
+            plan.close()
+        inserted = torch.zeros(V + Vn, dtype=torch.bool, device=vs.device)
+        inserted[V:] = True
+        if fair_steps > 0 and Vn > 0:
+            out_vs = prepare.laplacian_smooth(out_vs, out_faces, steps=fair_steps, movable=inserted)
+        st.mark("fair")
+        return Filled(out_vs, out_faces, V, F, inserted, loops, filled, st.result())
+
+
+def cut_torus(nu: int, nv: int, n_discs: int, frac: float = 0.05, device=None):
+    """``synth.torus_mesh(nu, nv)`` with ``n_discs`` graph-geodesic discs removed, as (vs float32, faces int64) device
+    tensors without the removed vertices.  The discs have the ring count ``synth.make_v_mask`` gives ``n_discs`` holes that
+    total ``frac`` of the vertices; their centres sit on a regular grid of the torus' parameter plane, far enough apart
+    that no two discs touch."""
+    from . import meshprep, synth
+    m = synth.torus_mesh(nu, nv, masks=False)
+    V = m.num_vertices
+    target = frac * V / max(n_discs, 1)
+    rings = max(1, int(round((math.sqrt(max(12 * target - 3, 0.0)) - 3) / 6)))      # synth.make_v_mask
+    gu = max(1, int(math.ceil(math.sqrt(n_discs * nu / nv))))
+    gv = max(1, int(math.ceil(n_discs / gu)))
+    if n_discs > 0 and min(nu // gu, nv // gv) < 2 * rings + 3:
+        raise ValueError(f"cut_torus: {n_discs} discs of {rings} rings do not fit a {nu} x {nv} torus without touching")
+    cells = [(a, b) for a in range(gu) for b in range(gv)][:n_discs]
+    seeds = np.array([((a * nu) // gu + nu // (2 * gu)) * nv + (b * nv) // gv + nv // (2 * gv) for a, b in cells], np.int64)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    faces = torch.from_numpy(m.faces).to(dev)
+    vs = torch.from_numpy(m.vs.astype(np.float32)).to(dev)
+    if n_discs == 0:
+        return vs, faces
+    topo = meshprep.MeshTopology(faces, V, dev, with_f2f=False)
+    seed_mask = torch.zeros((V, 1), dtype=torch.bool, device=dev)
+    seed_mask[torch.from_numpy(seeds).to(dev)] = True
+    hole = meshprep.dilate(topo, seed_mask, rings)[:, 0]
+    keep_f = ~hole[faces].any(1)
+    faces = faces[keep_f]
+    used = torch.zeros(V, dtype=torch.bool, device=dev)
+    used[faces.reshape(-1)] = True
+    new_id = torch.cumsum(used.to(torch.int64), 0) - 1
+    return vs[used].contiguous(), new_id[faces].contiguous()
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m semigcn_amd.holes",
+                                 description="close the holes of a triangle mesh (the hole filling of MeshFix.repair())")
+    ap.add_argument("--scan", help="the mesh with holes (OBJ)")
+    ap.add_argument("--out", help="where the filled mesh goes (OBJ)")
+    ap.add_argument("--max-hole-edges", type=int, default=None, help="leave loops with more edges open (default: fill all)")
+    ap.add_argument("--fair-steps", type=int, default=prepare.SMOOTH_ITER, help="smoothing steps on the inserted vertices")
+    ap.add_argument("--torus", type=int, nargs=2, metavar=("NU", "NV"), help="run on a synthetic torus instead of --scan")
+    ap.add_argument("--cut", type=int, default=40, help="with --torus: the number of discs removed")
+    ap.add_argument("--repeat", type=int, default=1, help="run this many times and report the last (the first ones warm up)")
+    args = ap.parse_args(argv)
+    if (args.scan is None) == (args.torus is None):
+        ap.error("give exactly one of --scan and --torus")
+    if args.scan is not None and args.out is None:
+        ap.error("--scan needs --out")
+    if args.fair_steps < 0 or args.repeat < 1 or args.cut < 0:
+        ap.error("--fair-steps, --cut must be >= 0 and --repeat >= 1")
+    if args.max_hole_edges is not None and args.max_hole_edges < 0:
+        ap.error("--max-hole-edges must be >= 0")
+    mesh = read_obj(args.scan) if args.scan is not None else cut_torus(args.torus[0], args.torus[1], args.cut)
+    for _ in range(args.repeat):
+        out = fill_holes(mesh, max_hole_edges=args.max_hole_edges, fair_steps=args.fair_steps, timings=True)
+    if args.out:
+        prepare.write_obj(args.out, out.vs, out.faces)
+    rec = {"n_vertices": out.num_original_vertices, "n_faces": out.num_original_faces, "n_loops": len(out.loops),
+           "n_filled": int(out.filled.sum()), "n_inserted_vertices": int(out.vs.shape[0] - out.num_original_vertices),
+           "n_inserted_faces": int(out.faces.shape[0] - out.num_original_faces), "fair_steps": args.fair_steps}
+    rec.update({k: round(v, 4) for k, v in out.stage_ms.items()})
+    print(json.dumps(rec))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
