@@ -429,6 +429,45 @@ SG_API int sg_fill_plan(sg_fill* s, int64_t max_hole_edges, void* stream, int64_
 SG_API int sg_fill_emit(sg_fill* s, const float* vs, float* new_vs, int64_t* new_faces, uint8_t* filled_out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Connected components -- replaces the first step of MeshFix.repair()
+ * (preprocess/prepare.py:28-33): label the components of a triangle list, keep
+ * some of them, compact vertices and faces.  The definitions (connectivities,
+ * degenerate faces, numbering, tie rule) are specified in
+ * semigcn_amd/components.py.
+ *
+ * sg_parts_create: labels the faces of faces int64 [F,3] over V vertices.
+ *   connectivity 0 ("edge"): two faces are connected when they share an
+ *   undirected edge; 1 ("vertex"): when they share a vertex.  A face with a
+ *   repeated vertex is degenerate: label -1, connected to nothing, never kept,
+ *   counted.  Components are numbered 0 .. K-1 by ascending smallest face.  A
+ *   vertex index outside [0, V), 3 F >= 2^31 or V >= 2^31 gives SG_ERR_INVALID.
+ *   F = 0 is valid (K = 0).  The plan keeps its own copy of the faces.
+ *   Synchronises the stream.
+ * sg_parts_query: info[8] (host) = K, F, V, degenerate faces, id of the largest
+ *   component (most faces; ties: the lower id; -1 when K = 0), its face count,
+ *   V' and F' of the last sg_parts_select (-1: none yet).
+ * sg_parts_labels: writes face_label int64 [F] (-1 = degenerate) and face_count
+ *   int64 [K] to device arrays of the caller.
+ * sg_parts_select: keep uint8 [K] on the device.  A face is kept when its
+ *   component is, a vertex when a kept face uses it.  Returns the numbers of
+ *   kept vertices and faces.  May be called again with another keep.
+ *   Synchronises the stream.
+ * sg_parts_emit: the stable compaction of the last select (kept vertices and
+ *   faces keep their relative order): new_vs float32 [V',3] copied bit for bit
+ *   from the kept rows of vs float32 [V,3], new_faces int64 [F',3] renumbered,
+ *   vertex_ids int64 [V'] and face_ids int64 [F'] new to old.  Fails before a
+ *   select.  Asynchronous.
+ * ------------------------------------------------------------------------- */
+typedef struct sg_parts sg_parts;
+SG_API int sg_parts_create(const int64_t* faces, int64_t F, int64_t V, int connectivity, void* stream, sg_parts** out);
+SG_API int sg_parts_destroy(sg_parts* p);
+SG_API int sg_parts_query(const sg_parts* p, int64_t* info);
+SG_API int sg_parts_labels(const sg_parts* p, int64_t* face_label, int64_t* face_count, void* stream);
+SG_API int sg_parts_select(sg_parts* p, const uint8_t* keep, void* stream, int64_t* n_vertices, int64_t* n_faces);
+SG_API int sg_parts_emit(sg_parts* p, const float* vs, float* new_vs, int64_t* new_faces, int64_t* vertex_ids, int64_t* face_ids,
+                         void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Loss step of the training loop, fused -- replaces Models.compute_fn
  * (util/models.py:121-126), Loss.mask_pos_rec_loss (util/loss.py:14-34, 'rmse')
  * and Loss.mask_norm_rec_loss (util/loss.py:78-107, 'l1mae') as sgcn.py:130-132

@@ -210,6 +210,12 @@ _SIGNATURES = {
     "sg_fill_loops": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_fill_plan": (c_int, [c_void_p, c_int64, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
     "sg_fill_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_parts_create": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, POINTER(c_void_p)]),
+    "sg_parts_destroy": (c_int, [c_void_p]),
+    "sg_parts_query": (c_int, [c_void_p, POINTER(c_int64)]),
+    "sg_parts_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_parts_select": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    "sg_parts_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -1509,6 +1515,100 @@ class FillPlan:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             load().sg_fill_destroy(self._h)
+            self._h = c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PartsPlan:
+    """Owns one sg_parts (csrc/mesh_parts.hip): the connected components of a triangle list (the definitions are specified
+    in semigcn_amd/components.py).  ``select`` marks what a ``keep`` over the components retains, ``emit`` writes the
+    compacted mesh of the last ``select``; ``select`` may be called again with another ``keep``."""
+
+    CONNECTIVITY = {"edge": 0, "vertex": 1}
+
+    def __init__(self, faces: torch.Tensor, num_vertices: int, connectivity: str = "edge"):
+        if connectivity not in self.CONNECTIVITY:
+            raise ValueError(f"connectivity must be 'edge' or 'vertex', got {connectivity!r}")
+        _require_device(faces, "faces")
+        if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
+            raise SemigcnLibraryError(f"faces must be int64 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+        faces = faces.contiguous()
+        self.device, self.num_vertices, self.num_faces = faces.device, int(num_vertices), faces.shape[0]
+        self.connectivity = connectivity
+        self._h = c_void_p(0)
+        out = c_void_p()
+        with _on_device(faces.device):
+            _check(load().sg_parts_create(_ptr(faces), faces.shape[0], self.num_vertices, self.CONNECTIVITY[connectivity],
+                                          _stream(faces), byref(out)), "sg_parts_create")
+        self._h = out
+        info = self._query()
+        self.num_components, _, _, self.n_degenerate, self.largest, self.largest_faces = (int(v) for v in info[:6])
+        self.num_kept_vertices = self.num_kept_faces = None
+
+    def _query(self):
+        info = (c_int64 * 8)()
+        _check(load().sg_parts_query(self._h, info), "sg_parts_query")
+        return list(info)
+
+    def _open(self):
+        if not self._h.value:
+            raise SemigcnLibraryError("PartsPlan is closed")
+
+    def labels(self):
+        """(face_label int64 [F], -1 = degenerate; face_count int64 [K]) on the plan's device."""
+        self._open()
+        label = torch.empty(max(self.num_faces, 1), dtype=torch.int64, device=self.device)
+        count = torch.empty(max(self.num_components, 1), dtype=torch.int64, device=self.device)
+        with _on_device(self.device):
+            _check(load().sg_parts_labels(self._h, _ptr(label), _ptr(count), _stream(label)), "sg_parts_labels")
+        return label[: self.num_faces], count[: self.num_components]
+
+    def select(self, keep: torch.Tensor):
+        """(kept vertices, kept faces) for ``keep`` bool / uint8 [K] on the plan's device (non-zero = keep)."""
+        self._open()
+        _require_device(keep, "keep")
+        if keep.numel() != self.num_components or keep.device != self.device:
+            raise SemigcnLibraryError(f"keep must hold {self.num_components} entries on {self.device}, got "
+                                      f"{tuple(keep.shape)} on {keep.device}")
+        keep = (keep.reshape(-1) != 0).contiguous()                # bool: one byte per component, 0 / 1
+        nv, nf = c_int64(), c_int64()
+        with _on_device(self.device):
+            _check(load().sg_parts_select(self._h, _ptr(keep) if self.num_components else None, _raw_stream_of(self.device),
+                                          byref(nv), byref(nf)), "sg_parts_select")
+        self.num_kept_vertices, self.num_kept_faces = int(nv.value), int(nf.value)
+        return self.num_kept_vertices, self.num_kept_faces
+
+    def emit(self, vs: torch.Tensor):
+        """(new_vs float32 [V', 3], new_faces int64 [F', 3], vertex_ids int64 [V'], face_ids int64 [F']) of the last
+        ``select``: the kept rows of ``vs`` bit for bit and the kept faces renumbered, both in their old order."""
+        self._open()
+        if self.num_kept_vertices is None:
+            raise SemigcnLibraryError("PartsPlan.emit: call select() first")
+        _require_device(vs, "vs")
+        if vs.dtype != torch.float32 or tuple(vs.shape) != (self.num_vertices, 3):
+            raise SemigcnLibraryError(f"vs must be float32 [{self.num_vertices}, 3], got {vs.dtype} {tuple(vs.shape)}")
+        if vs.device != self.device:
+            raise SemigcnLibraryError(f"vs on {vs.device}, plan on {self.device}")
+        vs = vs.detach().contiguous()
+        nv, nf = self.num_kept_vertices, self.num_kept_faces
+        new_vs = torch.empty((nv, 3), dtype=torch.float32, device=self.device)
+        new_faces = torch.empty((nf, 3), dtype=torch.int64, device=self.device)
+        vertex_ids = torch.empty(nv, dtype=torch.int64, device=self.device)
+        face_ids = torch.empty(nf, dtype=torch.int64, device=self.device)
+        none_if_empty = lambda t: _ptr(t) if t.numel() else None
+        with _on_device(self.device):
+            _check(load().sg_parts_emit(self._h, none_if_empty(vs), none_if_empty(new_vs), none_if_empty(new_faces),
+                                        none_if_empty(vertex_ids), none_if_empty(face_ids), _stream(vs)), "sg_parts_emit")
+        return new_vs, new_faces, vertex_ids, face_ids
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            load().sg_parts_destroy(self._h)
             self._h = c_void_p(0)
 
     def __del__(self):

@@ -599,6 +599,49 @@ SG_API int sg_fill_emit(sg_fill* s, const float* vs, float* new_vs, int64_t* new
   return fill_emit(s, vs, new_vs, new_faces, filled_out, (hipStream_t)stream);
 }
 
+// the component selection of MeshFix.repair() (preprocess/prepare.py:28-33): csrc/mesh_parts.hip
+SG_API int sg_parts_create(const int64_t* faces, int64_t F, int64_t V, int connectivity, void* stream, sg_parts** out) {
+  SG_REQUIRE(out != nullptr, "sg_parts_create: null out");
+  *out = nullptr;
+  SG_REQUIRE(F >= 0 && V >= 0, "sg_parts_create: negative size (F = %lld, V = %lld)", (long long)F, (long long)V);
+  SG_REQUIRE(connectivity == 0 || connectivity == 1, "sg_parts_create: connectivity must be 0 (edge) or 1 (vertex), got %d",
+             connectivity);
+  SG_REQUIRE(F == 0 || faces, "sg_parts_create: null pointer");
+  return parts_create(faces, F, V, connectivity, (hipStream_t)stream, out);
+}
+
+SG_API int sg_parts_destroy(sg_parts* p) {
+  destroy_parts(p);
+  return SG_OK;
+}
+
+SG_API int sg_parts_query(const sg_parts* p, int64_t* info) {
+  SG_REQUIRE(p != nullptr, "sg_parts_query: null plan");
+  SG_REQUIRE(info != nullptr, "sg_parts_query: null pointer");
+  parts_query(p, info);
+  return SG_OK;
+}
+
+SG_API int sg_parts_labels(const sg_parts* p, int64_t* face_label, int64_t* face_count, void* stream) {
+  SG_REQUIRE(p != nullptr, "sg_parts_labels: null plan");
+  return parts_labels(p, face_label, face_count, (hipStream_t)stream);
+}
+
+SG_API int sg_parts_select(sg_parts* p, const uint8_t* keep, void* stream, int64_t* n_vertices, int64_t* n_faces) {
+  SG_REQUIRE(p != nullptr, "sg_parts_select: null plan");
+  SG_REQUIRE(n_vertices && n_faces, "sg_parts_select: null pointer");
+  int64_t info[8];
+  parts_query(p, info);
+  SG_REQUIRE(info[0] == 0 || keep, "sg_parts_select: null pointer");
+  return parts_select(p, keep, (hipStream_t)stream, n_vertices, n_faces);
+}
+
+SG_API int sg_parts_emit(sg_parts* p, const float* vs, float* new_vs, int64_t* new_faces, int64_t* vertex_ids, int64_t* face_ids,
+                         void* stream) {
+  SG_REQUIRE(p != nullptr, "sg_parts_emit: null plan");
+  return parts_emit(p, vs, new_vs, new_faces, vertex_ids, face_ids, (hipStream_t)stream);
+}
+
 SG_API int sg_mesh_loss_bwd_det(const float* pos, const int64_t* faces, const float* target_pos, const float* v_keep,
                                 const float* target_fn, const float* f_keep, const float* g, int64_t V, int64_t V_ext,
                                 int64_t F, const sg_pool* incidence, float* corner_scratch, float* grad_pos, void* stream_) {

@@ -382,6 +382,14 @@ void fill_query(const sg_fill* s, int64_t* info);
 int fill_loops(const sg_fill* s, int64_t* loop_ptr_out, int64_t* loop_verts_out, hipStream_t stream);
 int fill_plan(sg_fill* s, int64_t max_hole_edges, hipStream_t stream, int64_t* n_new_vertices, int64_t* n_new_faces);
 int fill_emit(sg_fill* s, const float* vs, float* new_vs, int64_t* new_faces, uint8_t* filled_out, hipStream_t stream);
+// mesh_parts.hip
+int parts_create(const int64_t* faces, int64_t F, int64_t V, int connectivity, hipStream_t stream, sg_parts** out);
+void destroy_parts(sg_parts* s);
+void parts_query(const sg_parts* s, int64_t* info);
+int parts_labels(const sg_parts* s, int64_t* face_label, int64_t* face_count, hipStream_t stream);
+int parts_select(sg_parts* s, const uint8_t* keep, hipStream_t stream, int64_t* n_vertices, int64_t* n_faces);
+int parts_emit(sg_parts* s, const float* vs, float* new_vs, int64_t* new_faces, int64_t* vertex_ids, int64_t* face_ids,
+               hipStream_t stream);
 
 // trace.hip -- optional per-launch event timing (sg_trace_*)
 extern std::atomic<bool> g_trace_on;

@@ -1,8 +1,9 @@
 """Close the holes of a scan on the device: boundary loops, one ring patch per loop, fairing of the inserted vertices.
 
 Replaces the hole-closing part of ``MeshFix.repair()`` in the reference's preprocess/prepare.py:28-33 -- the step that
-creates the vertices the network exists to place.  NOT replaced: MeshFix's other repairs (self-intersections, keeping the
-largest component) and the isotropic remesh of the whole surface that follows (preprocess/prepare.py:35-42).  MeshFix is
+creates the vertices the network exists to place.  Keeping the largest component, which MeshFix does first, is
+``components.keep_components``.  NOT replaced: MeshFix's repair of self-intersections and the isotropic remesh of the
+whole surface that follows (preprocess/prepare.py:35-42).  MeshFix is
 not available to compare against; the construction below is this module's own and is the specification the tests pin
 (tests/holes_oracle.py restates it in numpy / float64).  The kernels are csrc/mesh_fill.hip; the fairing is
 ``prepare.laplacian_smooth`` (csrc/mesh_smooth.hip) with only the inserted vertices movable.
@@ -40,12 +41,14 @@ Inputs are what ``evaluate`` accepts; HIP device only: a CPU tensor raises ``Sem
 
 Command line::
 
-    python -m semigcn_amd.holes --scan A.obj --out A_filled.obj [--max-hole-edges N] [--fair-steps K]
+    python -m semigcn_amd.holes --scan A.obj --out A_filled.obj [--max-hole-edges N] [--fair-steps K] [--largest-component]
     python -m semigcn_amd.holes --torus NU NV --cut K [--out A_filled.obj]
 
 prints one JSON line with ``n_loops``, ``n_filled``, ``n_inserted_vertices``, ``n_inserted_faces`` and the device time of
 each stage (``loops_ms``, ``emit_ms``, ``fair_ms``).  ``--torus NU NV --cut K`` runs on ``synth.torus_mesh(NU, NV)``
 with K discs removed, sized as ``synth.make_v_mask`` sizes its holes (5 % of the vertices in all).
+``--largest-component`` first runs ``components.keep_components(..., keep="largest")`` and adds ``n_components`` and
+``n_dropped_faces`` to the line.
 """
 from __future__ import annotations
 
@@ -221,6 +224,8 @@ def main(argv=None) -> int:
     ap.add_argument("--torus", type=int, nargs=2, metavar=("NU", "NV"), help="run on a synthetic torus instead of --scan")
     ap.add_argument("--cut", type=int, default=40, help="with --torus: the number of discs removed")
     ap.add_argument("--repeat", type=int, default=1, help="run this many times and report the last (the first ones warm up)")
+    ap.add_argument("--largest-component", action="store_true",
+                    help="keep only the largest connected component before filling (components.keep_components)")
     args = ap.parse_args(argv)
     if (args.scan is None) == (args.torus is None):
         ap.error("give exactly one of --scan and --torus")
@@ -231,6 +236,12 @@ def main(argv=None) -> int:
     if args.max_hole_edges is not None and args.max_hole_edges < 0:
         ap.error("--max-hole-edges must be >= 0")
     mesh = read_obj(args.scan) if args.scan is not None else cut_torus(args.torus[0], args.torus[1], args.cut)
+    extra = {}
+    if args.largest_component:
+        from .components import keep_components
+        kept = keep_components(mesh, keep="largest")
+        extra = {"n_components": len(kept.components), "n_dropped_faces": int(mesh[1].shape[0] - kept.faces.shape[0])}
+        mesh = (kept.vs, kept.faces)
     for _ in range(args.repeat):
         out = fill_holes(mesh, max_hole_edges=args.max_hole_edges, fair_steps=args.fair_steps, timings=True)
     if args.out:
@@ -239,6 +250,7 @@ def main(argv=None) -> int:
            "n_filled": int(out.filled.sum()), "n_inserted_vertices": int(out.vs.shape[0] - out.num_original_vertices),
            "n_inserted_faces": int(out.faces.shape[0] - out.num_original_faces), "fair_steps": args.fair_steps}
     rec.update({k: round(v, 4) for k, v in out.stage_ms.items()})
+    rec.update(extra)
     print(json.dumps(rec))
     return 0
 
