@@ -356,6 +356,36 @@ SG_API int sg_mesh_distance_reduce(const float* q, const float* q_org, float eps
                                    const float* gt_vs, int64_t N, uint8_t* hole_out, double* out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Self-intersections -- the pair query behind the third part of
+ * MeshFix.repair() (preprocess/prepare.py:28-33): which faces of a surface
+ * cross which.  The predicate (float64 signs on the float32 coordinates, no
+ * epsilon, touching counts) is specified in semigcn_amd/repair.py.
+ *
+ * Both calls walk an sg_surface against itself; vs float32 [V,3] and faces
+ * int64 [F,3] are the arrays the surface was built from (the predicate reads
+ * them, not the surface's rounded copies) and F its face count.  F < 0, F
+ * beyond the int32 face ids, a null pointer, a null surface or an F that is
+ * not the surface's give SG_ERR_INVALID before the device is touched; F == 0
+ * returns SG_OK without a launch and without reading any argument.
+ *
+ * sg_surface_self_count: n_any int32 [F] = partners j != i of face i, n_upper
+ *   int32 [F] = partners j > i, stats_dev int64 [2] (device): [0] = faces with
+ *   a repeated vertex id or a zero normal (they take part in no pair), [1] =
+ *   subtrees the walk had to drop because its stack was full -- 0 for every
+ *   tree sg_surface_create builds; a caller that reads anything else must
+ *   discard the counts.  Asynchronous; integer atomics only: deterministic.
+ * sg_surface_self_pairs: offsets int64 [F+1] = the exclusive scan of n_upper
+ *   (offsets[F] = n_pairs); writes pairs int64 [n_pairs,2] in canonical order:
+ *   i < j, rows sorted lexicographically.  n_pairs < 0 or >= 2^31 gives
+ *   SG_ERR_INVALID; n_pairs == 0 returns SG_OK without a launch.
+ *   Asynchronous; two runs give identical bytes.
+ * ------------------------------------------------------------------------- */
+SG_API int sg_surface_self_count(const sg_surface* s, const float* vs, const int64_t* faces, int64_t F, int32_t* n_any,
+                                 int32_t* n_upper, int64_t* stats_dev, void* stream);
+SG_API int sg_surface_self_pairs(const sg_surface* s, const float* vs, const int64_t* faces, int64_t F,
+                                 const int64_t* offsets, int64_t n_pairs, int64_t* pairs, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Network inputs from a remeshed scan -- replaces the tail of
  * preprocess/prepare.py: edge_based_scaling (:48-52) and smooth (:110-114,
  * pymeshlab's laplacian_smooth with stepsmoothnum=30, cotangentweight=False).

@@ -197,6 +197,8 @@ _SIGNATURES = {
     "sg_surface_create": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, POINTER(c_void_p)]),
     "sg_surface_destroy": (c_int, [c_void_p]),
     "sg_surface_query": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_surface_self_count": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_surface_self_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "sg_mesh_distance_reduce": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                         c_void_p]),
     "sg_edge_length_blocks": (c_int64, [c_int64]),
@@ -1321,6 +1323,43 @@ class SurfaceHandle:
             _check(load().sg_surface_query(self._h, _ptr(pts), N, int(bool(signed)), _ptr(dist), _ptr(face), _ptr(closest),
                                            _stream(pts)), "sg_surface_query")
         return dist, face, closest
+
+    def _self_args(self, vs: torch.Tensor, faces: torch.Tensor):
+        for t, n in ((vs, "vs"), (faces, "faces")):
+            _require_device(t, n)
+            if t.device != self.device:
+                raise SemigcnLibraryError(f"{n} on {t.device}, surface on {self.device}")
+        if vs.dtype != torch.float32 or tuple(vs.shape) != (self.num_vertices, 3) or not vs.is_contiguous():
+            raise SemigcnLibraryError(f"vs must be the contiguous float32 [{self.num_vertices}, 3] the surface was built from, "
+                                      f"got {vs.dtype} {tuple(vs.shape)}")
+        if faces.dtype != torch.int64 or tuple(faces.shape) != (self.num_faces, 3) or not faces.is_contiguous():
+            raise SemigcnLibraryError(f"faces must be the contiguous int64 [{self.num_faces}, 3] the surface was built from, "
+                                      f"got {faces.dtype} {tuple(faces.shape)}")
+
+    def self_count(self, vs: torch.Tensor, faces: torch.Tensor):
+        """(n_any int32 [F], n_upper int32 [F], stats int64 [2] = degenerate faces, dropped subtrees) of
+        sg_surface_self_count, on the device."""
+        self._self_args(vs, faces)
+        F = self.num_faces
+        n_any = torch.empty(F, dtype=torch.int32, device=self.device)
+        n_upper = torch.empty(F, dtype=torch.int32, device=self.device)
+        n_deg = torch.zeros(2, dtype=torch.int64, device=self.device)
+        with _on_device(self.device):
+            _check(load().sg_surface_self_count(self._h, _ptr(vs), _ptr(faces), F, _ptr(n_any), _ptr(n_upper), _ptr(n_deg),
+                                                _stream(vs)), "sg_surface_self_count")
+        return n_any, n_upper, n_deg
+
+    def self_pairs(self, vs: torch.Tensor, faces: torch.Tensor, offsets: torch.Tensor, n_pairs: int) -> torch.Tensor:
+        """pairs int64 [n_pairs, 2] in canonical order (sg_surface_self_pairs); offsets int64 [F + 1] on the device."""
+        self._self_args(vs, faces)
+        _require_device(offsets, "offsets")
+        if offsets.dtype != torch.int64 or offsets.numel() != self.num_faces + 1 or not offsets.is_contiguous():
+            raise SemigcnLibraryError(f"offsets must be contiguous int64 [{self.num_faces + 1}]")
+        pairs = torch.empty((int(n_pairs), 2), dtype=torch.int64, device=self.device)
+        with _on_device(self.device):
+            _check(load().sg_surface_self_pairs(self._h, _ptr(vs), _ptr(faces), self.num_faces, _ptr(offsets), int(n_pairs),
+                                                _ptr(pairs), _stream(vs)), "sg_surface_self_pairs")
+        return pairs
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -17,28 +17,16 @@
 // error then scales with the distance and the triangle size, not with the coordinates.
 #include <hipcub/hipcub.hpp>
 
-#include "sg_common.h"
-
-struct sg_surface {
-  int64_t V = 0, F = 0, L = 0;   // vertices, faces, leaves
-  float4* tri = nullptr;         // [3F] in leaf order: (a, face id bits), (b - a, 0), (c - a, 0)
-  float4* nodes = nullptr;       // [max(L - 1, 1)][4]: child 0 lo (w: child code), hi, child 1 lo (w: code), hi
-  float* bounds = nullptr;       // [6] box of the face centroids (the query points' Morton frame)
-};
+#include "mesh_bvh.h"   // struct sg_surface, kLeaf, kStack, the child codes
 
 namespace sg {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kLeaf = 4;          // faces per leaf
-constexpr int kStack = 64;        // a Karras tree over 64-bit keys is at most 64 internal levels deep
 constexpr int kQueryThreads = 64; // one wavefront per workgroup: its stack is 64 x 64 int32 = 16 KiB of LDS
 constexpr int kRedBlocks = 1024;  // fixed grid of the metric reduction: a fixed summation order
 
 inline int blocks_for(int64_t n) { return (int)((n + kThreads - 1) / kThreads); }
-
-// Child codes: >= 0 internal node, < 0 leaf ~code.
-__device__ __forceinline__ float code_bits(int c) { return __int_as_float(c); }
 
 __device__ __forceinline__ uint64_t spread3(uint64_t x) {   // 21 bits -> every third bit of 63
   x &= 0x1fffffull;

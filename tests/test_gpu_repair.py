@@ -1,0 +1,188 @@
+"""semigcn_amd.repair on the device against the numpy restatement in tests/intersect_oracle.py.  Every comparison of pairs
+is exact: on integer coordinates the oracle evaluates in int64, on the float case it reports no marginal pair (checked
+here), so the sign of every determinant is beyond doubt; there is no tolerance anywhere.
+
+Shapes: the hand cases (one per branch of the predicate, F = 2 or 3: a lone leaf); two interpenetrating cubes with F = 299
+(a partial leaf, a partial wavefront, five workgroups), also under a face permutation; a flat grid (all coplanar); a rounded
+torus and sphere (clean); two jittered tori of 6 080 faces in float32; one face with 1 200 partners, as the first face and
+as the last; and the repair loop on a folded sphere."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import intersect_oracle as IO
+from semigcn_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+
+
+def dev(x, dtype=None):
+    t = torch.from_numpy(np.array(x)).to(DEV)             # a copy: the shared fixtures are read-only
+    return t if dtype is None else t.to(dtype)
+
+
+def detect(vs, faces, **kw):
+    from semigcn_amd import repair
+    got = repair.self_intersections(dev(vs, torch.float32), dev(faces), **kw)
+    assert got.pairs.dtype == torch.int64 and got.pairs.dim() == 2 and got.pairs.shape[1] == 2
+    assert got.face_mask.dtype == torch.bool and tuple(got.face_mask.shape) == (np.asarray(faces).shape[0],)
+    return got
+
+
+def check(vs, faces, want=None):
+    """self_intersections on the device equals the oracle's pairs, mask and count; returns both."""
+    want = IO.self_intersections(vs, faces) if want is None else want
+    got = detect(vs, faces)
+    assert len(got) == len(want)
+    assert np.array_equal(got.pairs.cpu().numpy(), want.pairs)
+    assert np.array_equal(got.face_mask.cpu().numpy(), want.face_mask)
+    assert got.n_degenerate == want.n_degenerate
+    return got, want
+
+
+@functools.lru_cache(maxsize=None)
+def boxes():
+    vs, faces = IO.two_boxes()
+    return vs, faces, IO.self_intersections(vs, faces)
+
+
+# ---- integer coordinates ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(IO.hand_cases()))
+def test_hand_cases(name):
+    vs, faces, pairs, n_degenerate = IO.hand_cases()[name]
+    got, want = check(vs, faces)
+    assert want.pairs.tolist() == pairs.tolist() and got.n_degenerate == n_degenerate
+
+
+def test_two_boxes_equal_the_oracle_and_repeat_bit_for_bit():
+    vs, faces, want = boxes()
+    assert faces.shape[0] % 4 and faces.shape[0] % 64 and faces.shape[0] > 2 * 64 and len(want) > 0
+    got, _ = check(vs, faces, want)
+    assert got.pairs.cpu().numpy().tobytes() == want.pairs.tobytes()
+    in_pairs = np.zeros(faces.shape[0], bool)
+    in_pairs[got.pairs.cpu().numpy().reshape(-1)] = True
+    assert np.array_equal(got.face_mask.cpu().numpy(), in_pairs)
+    again = detect(vs, faces)
+    assert again.pairs.cpu().numpy().tobytes() == got.pairs.cpu().numpy().tobytes()
+    assert again.face_mask.cpu().numpy().tobytes() == got.face_mask.cpu().numpy().tobytes()
+
+
+def test_an_existing_surface_is_used():
+    from semigcn_amd import evaluate
+    vs, faces, want = boxes()
+    d_vs, d_faces = dev(vs, torch.float32), dev(faces)
+    s = evaluate.Surface(d_vs, d_faces)
+    try:
+        from semigcn_amd import repair
+        got = repair.self_intersections(s.vs, s.faces, surface=s)
+        assert np.array_equal(got.pairs.cpu().numpy(), want.pairs)
+        with pytest.raises(ValueError, match="surface"):
+            repair.self_intersections(d_vs, d_faces[:-1].contiguous(), surface=s)
+        with pytest.raises(ValueError, match="other arrays"):                # the same shapes, not the same arrays
+            repair.self_intersections(d_vs.clone(), d_faces.clone(), surface=s)
+    finally:
+        s.close()
+
+
+def test_face_order_does_not_matter():
+    vs, faces, want = boxes()
+    perm = np.random.default_rng(5).permutation(faces.shape[0])       # new face k is old face perm[k]
+    got = detect(vs, faces[perm])
+    back = np.sort(perm[got.pairs.cpu().numpy()], 1)
+    back = back[np.lexsort((back[:, 1], back[:, 0]))]
+    assert np.array_equal(back, want.pairs)
+
+
+def test_flat_grid_has_no_pair():
+    vs, faces = IO.flat_grid(8)
+    got, _ = check(vs, faces)
+    assert len(got) == 0 and not got.face_mask.any()
+
+
+@pytest.mark.parametrize("which", ["torus", "sphere"])
+def test_rounded_clean_meshes_have_no_pair(which):
+    mesh = synth.torus_mesh(20, 12) if which == "torus" else synth.octahedron_sphere(3)
+    vs, faces = IO.scaled_integers(mesh, 512)
+    got, _ = check(vs, faces)
+    assert len(got) == 0 and got.n_degenerate == 0
+
+
+# ---- float coordinates -----------------------------------------------------------------------------------------------------
+def test_jittered_torus_pair():
+    vs, faces = IO.torus_pair(40, 38, seed=314)
+    want = IO.self_intersections(vs, faces)
+    assert faces.shape[0] == 6080 and len(want) > 100
+    assert len(want.marginal) == 0           # a condition on the INPUT (this seed): every sign the oracle took is safe
+    check(vs, faces, want)
+
+
+# ---- one face with many partners -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("big_first", [True, False])
+def test_one_face_with_hundreds_of_partners(big_first):
+    """big_first: the large triangle is face 0, so ITS lane counts 1 200 partners and emits 1 200 rows across a gap of
+    1 200 in the offsets, with every other face's offset behind it.  Otherwise it is the last face: 1 200 lanes add to its
+    n_any and emit one row each."""
+    from semigcn_amd import evaluate
+    vs, faces = IO.crossed_grid(30, big_first)
+    big = 0 if big_first else faces.shape[0] - 1
+    got, want = check(vs, faces)                          # pairs (so every row's place), mask and counts equal the oracle's
+    pairs = got.pairs.cpu().numpy()
+    assert len(got) == 1200 and int((pairs[:, 0 if big_first else 1] == big).sum()) == 1200
+    if big_first:
+        assert np.array_equal(pairs[:, 1], np.flatnonzero(want.face_mask)[1:])        # the partners, ascending
+    # the per-face counts themselves
+    d_vs, d_faces = dev(vs, torch.float32), dev(faces)
+    s = evaluate.Surface(d_vs, d_faces)
+    try:
+        n_any, n_upper, stats = s._h.self_count(s.vs, s.faces)
+        torch.cuda.synchronize()
+    finally:
+        s.close()
+    assert np.array_equal(n_any.cpu().numpy(), np.bincount(want.pairs.reshape(-1), minlength=faces.shape[0]))
+    assert np.array_equal(n_upper.cpu().numpy(), np.bincount(want.pairs[:, 0], minlength=faces.shape[0]))
+    assert int(n_any[big]) == 1200 and int(n_upper[big]) == (1200 if big_first else 0) and stats.tolist() == [0, 0]
+
+
+# ---- the repair loop -------------------------------------------------------------------------------------------------------
+def test_repair_of_the_folded_sphere():
+    from semigcn_amd import components, holes, repair
+    vs, faces = IO.folded_sphere()
+    d_vs, d_faces = dev(vs), dev(faces)
+    assert len(repair.self_intersections(d_vs, d_faces)) > 0
+    out_vs, out_faces, report = repair.repair((d_vs, d_faces))
+    assert report.vs is out_vs and report.faces is out_faces
+    assert report.remaining == 0 == len(repair.self_intersections(out_vs, out_faces))
+    assert len(holes.boundary_loops(out_faces, out_vs.shape[0])) == 0
+    assert len(components.face_components(out_faces, out_vs.shape[0])) == 1
+    assert 1 <= report.rounds <= 10 and len(report.removed_per_round) == report.rounds
+    ids = report.vertex_ids.cpu().numpy()
+    assert ids.shape == (out_vs.shape[0],) and (ids == -1).any()
+    kept = ids >= 0
+    assert np.array_equal(out_vs.cpu().numpy()[kept].view(np.uint32), vs[ids[kept]].view(np.uint32))
+
+
+def test_max_rounds_zero_only_detects():
+    from semigcn_amd import repair
+    vs, faces = IO.folded_sphere()
+    d_vs, d_faces = dev(vs), dev(faces)
+    P = len(repair.self_intersections(d_vs, d_faces))
+    out = repair.remove_self_intersections((d_vs, d_faces), max_rounds=0)
+    assert out.rounds == 0 and out.removed_per_round == [] and out.remaining == P > 0
+    assert out.vs.cpu().numpy().tobytes() == vs.tobytes() and out.faces.cpu().numpy().tobytes() == faces.tobytes()
+    assert out.vertex_ids.cpu().numpy().tolist() == list(range(vs.shape[0]))
+
+
+def test_a_clean_mesh_comes_back_as_it_is():
+    from semigcn_amd import repair
+    m = synth.octahedron_sphere(3)
+    vs, faces = m.vs.astype(np.float32), m.faces
+    out = repair.remove_self_intersections((dev(vs), dev(faces)))
+    assert out.rounds == 0 and out.remaining == 0
+    assert out.vs.cpu().numpy().tobytes() == vs.tobytes() and out.faces.cpu().numpy().tobytes() == faces.tobytes()
+    out_vs, out_faces, report = repair.repair((dev(vs), dev(faces)))
+    assert report.rounds == 0 and report.remaining == 0
+    assert out_vs.cpu().numpy().tobytes() == vs.tobytes() and out_faces.cpu().numpy().tobytes() == faces.tobytes()
