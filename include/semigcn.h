@@ -498,6 +498,48 @@ SG_API int sg_parts_emit(sg_parts* p, const float* vs, float* new_vs, int64_t* n
                          void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Refining a mesh to a target edge length (csrc/mesh_remesh.hip): the edge
+ * splits and edge flips of the isotropic remesh in the reference's
+ * preprocess/prepare.py:35-42.  Edge collapse is not part of it.  The rules
+ * (priority, selection, numbering of what is inserted, the flip guard) are
+ * specified in semigcn_amd/remesh.py.
+ *
+ * sg_remesh_create: takes a copy of vs float32 [V,3] and faces int64 [F,3]
+ *   (device) and analyses it.  A vertex index outside [0, V), 3 F >= 2^31 or
+ *   V >= 2^31 gives SG_ERR_INVALID.  V = F = 0 is valid and touches no device.
+ *   Synchronises the stream.
+ * sg_remesh_query: info[16] (host) = V, F (current), undirected edges and
+ *   border edges of the input, edges with three or more faces, edges whose two
+ *   faces run them in the same direction, faces with a repeated vertex,
+ *   vertices with a non-finite coordinate, the smallest offending edge (lo, hi;
+ *   -1, -1: none), the smallest offending face, the smallest offending vertex,
+ *   V and F of the input, 1 when the input is valid (the four counts are 0),
+ *   0 (reserved).  sg_remesh_split / sg_remesh_flip refuse an invalid input.
+ * sg_remesh_split: rounds of edge splits until no edge has len2 > thr2 or
+ *   max_rounds rounds ran.  counts (host, int64 [max_rounds]) receives the
+ *   edges split per round, *n_rounds the rounds that split something, *n_long
+ *   the long edges left (0 unless max_rounds ran out).  One stream
+ *   synchronisation per round.
+ * sg_remesh_flip: rounds of edge flips until none is selected or max_rounds
+ *   rounds ran.  counts (host, int64 [max_rounds]) receives the flips per round,
+ *   deviation[2] (host) the sum of |valence - target| before and after.  One
+ *   stream synchronisation per round.
+ * sg_remesh_export: writes the current mesh to device arrays of the caller:
+ *   vs float32 [V,3], faces int64 [F,3], parents int64 [V,2] ((i, i) for a
+ *   vertex of the input, the two ends (lo, hi) of the split edge otherwise) and,
+ *   when not null, border uint8 [V] (1 = the vertex is on a border edge).
+ *   Asynchronous.
+ * ------------------------------------------------------------------------- */
+typedef struct sg_remesh sg_remesh;
+SG_API int sg_remesh_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, void* stream, sg_remesh** out);
+SG_API int sg_remesh_destroy(sg_remesh* p);
+SG_API int sg_remesh_query(const sg_remesh* p, int64_t* info);
+SG_API int sg_remesh_split(sg_remesh* p, float thr2, int64_t max_rounds, void* stream, int64_t* counts, int64_t* n_rounds,
+                           int64_t* n_long);
+SG_API int sg_remesh_flip(sg_remesh* p, int64_t max_rounds, void* stream, int64_t* counts, int64_t* n_rounds, int64_t* deviation);
+SG_API int sg_remesh_export(const sg_remesh* p, float* vs, int64_t* faces, int64_t* parents, uint8_t* border, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Loss step of the training loop, fused -- replaces Models.compute_fn
  * (util/models.py:121-126), Loss.mask_pos_rec_loss (util/loss.py:14-34, 'rmse')
  * and Loss.mask_norm_rec_loss (util/loss.py:78-107, 'l1mae') as sgcn.py:130-132

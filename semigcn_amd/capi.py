@@ -218,6 +218,12 @@ _SIGNATURES = {
     "sg_parts_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_parts_select": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
     "sg_parts_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_remesh_create": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, POINTER(c_void_p)]),
+    "sg_remesh_destroy": (c_int, [c_void_p]),
+    "sg_remesh_query": (c_int, [c_void_p, POINTER(c_int64)]),
+    "sg_remesh_split": (c_int, [c_void_p, c_float, c_int64, c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "sg_remesh_flip": (c_int, [c_void_p, c_int64, c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "sg_remesh_export": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -1648,6 +1654,100 @@ class PartsPlan:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             load().sg_parts_destroy(self._h)
+            self._h = c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RemeshPlan:
+    """Owns one sg_remesh (csrc/mesh_remesh.hip): a copy of a mesh on the device that ``split`` and ``flip`` refine in place
+    (the rules are specified in semigcn_amd/remesh.py) and ``export`` hands back.  ``n_nonmanifold`` / ``n_misoriented`` /
+    ``n_degenerate`` / ``n_nonfinite`` with ``bad_edge`` / ``bad_face`` / ``bad_vertex`` say why an input is refused;
+    ``split`` and ``flip`` then raise."""
+
+    def __init__(self, vs: torch.Tensor, faces: torch.Tensor):
+        _require_device(vs, "vs")
+        _require_device(faces, "faces")
+        if vs.dtype != torch.float32 or vs.dim() != 2 or vs.shape[1] != 3:
+            raise SemigcnLibraryError(f"vs must be float32 [V, 3], got {vs.dtype} {tuple(vs.shape)}")
+        if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
+            raise SemigcnLibraryError(f"faces must be int64 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+        if faces.device != vs.device:
+            raise SemigcnLibraryError(f"faces on {faces.device}, vs on {vs.device}")
+        vs, faces = vs.detach().contiguous(), faces.contiguous()
+        self.device = vs.device
+        self._h = c_void_p(0)
+        out = c_void_p()
+        with _on_device(self.device):
+            _check(load().sg_remesh_create(_ptr(vs), vs.shape[0], _ptr(faces), faces.shape[0], _stream(vs), byref(out)),
+                   "sg_remesh_create")
+        self._h = out
+        info = self._query()
+        (self.num_vertices, self.num_faces, self.num_edges, self.num_border_edges, self.n_nonmanifold, self.n_misoriented,
+         self.n_degenerate, self.n_nonfinite) = (int(v) for v in info[:8])
+        self.bad_edge = (int(info[8]), int(info[9]))
+        self.bad_face, self.bad_vertex = int(info[10]), int(info[11])
+        self.valid = bool(info[14])
+
+    def _query(self):
+        info = (c_int64 * 16)()
+        _check(load().sg_remesh_query(self._h, info), "sg_remesh_query")
+        return list(info)
+
+    def _open(self):
+        if not self._h.value:
+            raise SemigcnLibraryError("RemeshPlan is closed")
+
+    def _sizes(self):
+        self.num_vertices, self.num_faces = (int(v) for v in self._query()[:2])
+
+    def split(self, thr2: float, max_rounds: int = 64):
+        """(edges split per round, long edges left): rounds of edge splits until no ``len2 > thr2`` is left or
+        ``max_rounds`` rounds ran.  ``thr2`` is passed as a float32."""
+        self._open()
+        max_rounds = int(max_rounds)
+        counts = (c_int64 * max(max_rounds, 1))()
+        n_rounds, n_long = c_int64(), c_int64()
+        with _on_device(self.device):
+            _check(load().sg_remesh_split(self._h, c_float(thr2), max_rounds, _raw_stream_of(self.device), counts,
+                                          byref(n_rounds), byref(n_long)), "sg_remesh_split")
+        self._sizes()
+        return [int(c) for c in counts[: n_rounds.value]], int(n_long.value)
+
+    def flip(self, max_rounds: int = 32):
+        """(flips per round, deviation before, deviation after): rounds of edge flips until none is selected or
+        ``max_rounds`` rounds ran."""
+        self._open()
+        max_rounds = int(max_rounds)
+        counts = (c_int64 * max(max_rounds, 1))()
+        n_rounds = c_int64()
+        dev = (c_int64 * 2)()
+        with _on_device(self.device):
+            _check(load().sg_remesh_flip(self._h, max_rounds, _raw_stream_of(self.device), counts, byref(n_rounds), dev),
+                   "sg_remesh_flip")
+        return [int(c) for c in counts[: n_rounds.value]], int(dev[0]), int(dev[1])
+
+    def export(self):
+        """(vs float32 [V, 3], faces int64 [F, 3], parents int64 [V, 2], border bool [V]) of the mesh as it stands."""
+        self._open()
+        V, F = self.num_vertices, self.num_faces
+        vs = torch.empty((V, 3), dtype=torch.float32, device=self.device)
+        faces = torch.empty((F, 3), dtype=torch.int64, device=self.device)
+        parents = torch.empty((V, 2), dtype=torch.int64, device=self.device)
+        border = torch.empty(V, dtype=torch.bool, device=self.device)
+        none_if_empty = lambda t: _ptr(t) if t.numel() else None
+        with _on_device(self.device):
+            _check(load().sg_remesh_export(self._h, none_if_empty(vs), none_if_empty(faces), none_if_empty(parents),
+                                           none_if_empty(border), _stream(vs)), "sg_remesh_export")
+        return vs, faces, parents, border
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            load().sg_remesh_destroy(self._h)
             self._h = c_void_p(0)
 
     def __del__(self):

@@ -642,6 +642,48 @@ SG_API int sg_parts_emit(sg_parts* p, const float* vs, float* new_vs, int64_t* n
   return parts_emit(p, vs, new_vs, new_faces, vertex_ids, face_ids, (hipStream_t)stream);
 }
 
+// splitting and flipping of the isotropic remesh (preprocess/prepare.py:35-42): csrc/mesh_remesh.hip
+SG_API int sg_remesh_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, void* stream, sg_remesh** out) {
+  SG_REQUIRE(out != nullptr, "sg_remesh_create: null out");
+  *out = nullptr;
+  SG_REQUIRE(F >= 0 && V >= 0, "sg_remesh_create: negative size (V = %lld, F = %lld)", (long long)V, (long long)F);
+  SG_REQUIRE((V == 0 || vs) && (F == 0 || faces), "sg_remesh_create: null pointer");
+  return remesh_create(vs, V, faces, F, (hipStream_t)stream, out);
+}
+
+SG_API int sg_remesh_destroy(sg_remesh* p) {
+  destroy_remesh(p);
+  return SG_OK;
+}
+
+SG_API int sg_remesh_query(const sg_remesh* p, int64_t* info) {
+  SG_REQUIRE(p != nullptr, "sg_remesh_query: null plan");
+  SG_REQUIRE(info != nullptr, "sg_remesh_query: null pointer");
+  remesh_query(p, info);
+  return SG_OK;
+}
+
+SG_API int sg_remesh_split(sg_remesh* p, float thr2, int64_t max_rounds, void* stream, int64_t* counts, int64_t* n_rounds,
+                           int64_t* n_long) {
+  SG_REQUIRE(p != nullptr, "sg_remesh_split: null plan");
+  SG_REQUIRE(max_rounds >= 0, "sg_remesh_split: negative max_rounds (%lld)", (long long)max_rounds);
+  SG_REQUIRE(thr2 > 0.0f, "sg_remesh_split: thr2 must be positive");          // false for a NaN as well
+  SG_REQUIRE(n_rounds && n_long && (max_rounds == 0 || counts), "sg_remesh_split: null pointer");
+  return remesh_split(p, thr2, max_rounds, (hipStream_t)stream, counts, n_rounds, n_long);
+}
+
+SG_API int sg_remesh_flip(sg_remesh* p, int64_t max_rounds, void* stream, int64_t* counts, int64_t* n_rounds, int64_t* deviation) {
+  SG_REQUIRE(p != nullptr, "sg_remesh_flip: null plan");
+  SG_REQUIRE(max_rounds >= 0, "sg_remesh_flip: negative max_rounds (%lld)", (long long)max_rounds);
+  SG_REQUIRE(n_rounds && deviation && (max_rounds == 0 || counts), "sg_remesh_flip: null pointer");
+  return remesh_flip(p, max_rounds, (hipStream_t)stream, counts, n_rounds, deviation);
+}
+
+SG_API int sg_remesh_export(const sg_remesh* p, float* vs, int64_t* faces, int64_t* parents, uint8_t* border, void* stream) {
+  SG_REQUIRE(p != nullptr, "sg_remesh_export: null plan");
+  return remesh_export(p, vs, faces, parents, border, (hipStream_t)stream);
+}
+
 SG_API int sg_mesh_loss_bwd_det(const float* pos, const int64_t* faces, const float* target_pos, const float* v_keep,
                                 const float* target_fn, const float* f_keep, const float* g, int64_t V, int64_t V_ext,
                                 int64_t F, const sg_pool* incidence, float* corner_scratch, float* grad_pos, void* stream_) {

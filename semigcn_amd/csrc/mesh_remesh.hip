@@ -1,0 +1,673 @@
+// Refining a triangle mesh to a target edge length on the device: split long edges, flip edges towards regular valence.
+//
+// Replaces the splitting and flipping of the isotropic remesh the reference runs between MeshFix and the scaling
+// (preprocess/prepare.py:35-42); edge collapse is not part of it, and the relaxation / re-projection is plumbing over
+// mesh_smooth.hip and mesh_dist.hip.  The specification is semigcn_amd/remesh.py; in short:
+//
+//   analysis   every round starts from the same analysis of the mesh it finds: half-edge h = 3 f + k is keyed lo * V + hi
+//              (undirected) with h as the value; one radix sort over the 3 F pairs, restricted to the bits V * V needs, puts
+//              the faces of an edge side by side (the sort is stable: a run lists its half-edges in ascending h).  Run
+//              heads, an inclusive scan of the heads (the edge rank r in ascending (lo, hi) order), the rank of every
+//              half-edge, border vertices, and -- only ever non-zero for the caller's input -- the counts of edges with
+//              three or more faces, of pairs that run an edge in the same direction, and the smallest such edge.
+//   split      face pass: the long edge of highest priority (len2 bits << 32 | hash(r)) of every face.  Edge pass: a long
+//              edge is selected when it is that edge in each of its faces, and marks its faces.  Two exclusive scans number
+//              the selected edges (new vertex V + s) and the split faces (new face F + t); ONE host synchronisation reads
+//              both totals, grows the buffers when needed, and the emit writes midpoints, parents and faces in place.
+//   flip       valence by integer atomicAdd per edge end; candidates with their gain and guard, keyed gain << 32 | hash(r),
+//              a 64-bit atomicMax of the key into the slot of each of the four vertices; a check pass (a candidate wins when
+//              all four slots hold its key); ONE host synchronisation reads the number of winners and the deviation; the
+//              apply pass rewrites the two faces of every winner.  Winners are vertex-disjoint, hence face-disjoint.
+//
+// hash is the 32-bit mixer x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16: a bijection, so two
+// edges never tie and the order in which the atomics arrive cannot matter.  There are no float atomics; integer max and
+// integer sums do not depend on order: every output is deterministic.  The float arithmetic is the squared length, the
+// midpoint and the float64 guard, each a fixed sequence of multiplies and adds: this file is built with -ffp-contract=off.
+#include <hipcub/hipcub.hpp>
+
+#include <initializer_list>
+#include <new>
+
+#include "sg_common.h"
+
+namespace sg {
+namespace {
+
+// a device buffer that only grows; `keep` carries the old bytes over
+struct Buf {
+  void* p = nullptr;
+  size_t cap = 0;
+};
+
+// slots of the counter block
+enum {
+  kOutOfRange = 0, kDegenerate, kBadFace, kNonFinite, kBadVertex, kNonManifold, kMisoriented, kBadKey, kBorderEdges, kEdges,
+  kLong, kWinners, kDeviation, kTotalA, kTotalF, kCounters = 16
+};
+
+}  // namespace
+}  // namespace sg
+
+struct sg_remesh {
+  int64_t V = 0, F = 0, V0 = 0, F0 = 0;
+  unsigned long long h_ctr[sg::kCounters] = {};     // the counters of the creating analysis (validation)
+  int64_t bad_key_V = 0;                            // the V that the smallest offending key was formed with
+  bool valid = false;
+  sg::Buf vs, par, tri, border;                     // the mesh: float [V][3], int32 [V][2], int32 [F][3], uint8 [V]
+  sg::Buf keys_a, keys_b, vals_a, vals_b, head, incl, he_rank, best, fpos, flag_a, scan_a, flag_f, scan_f, cand, win, slot, val,
+      temp, ctr;
+};
+
+namespace sg {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr float kHalf = 0.5f;
+
+inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+
+int reserve(Buf* b, size_t bytes, bool keep, hipStream_t stream) {
+  if (bytes <= b->cap) return SG_OK;
+  SG_HIP_TRY(hipStreamSynchronize(stream));          // nothing in flight reads what is freed below
+  size_t want = b->cap + b->cap / 2;
+  if (want < bytes) want = bytes;
+  if (want < 256) want = 256;
+  void* q = nullptr;
+  SG_HIP_TRY(hipMalloc(&q, want));
+  if (keep && b->p && b->cap) {
+    hipError_t e = hipMemcpyAsync(q, b->p, b->cap, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+      (void)hipFree(q);
+      SG_HIP_TRY(e);
+    }
+  }
+  if (b->p) (void)hipFree(b->p);
+  b->p = q;
+  b->cap = want;
+  return SG_OK;
+}
+
+__device__ inline uint32_t hash32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+
+__device__ inline int next3(int k) { return k == 2 ? 0 : k + 1; }
+
+// len2 of the edge {a, b}: d = vs[hi] - vs[lo], dx * dx + dy * dy + dz * dz, left to right, float32
+__device__ inline float edge_len2(const float* __restrict__ vs, int32_t a, int32_t b) {
+  const int32_t lo = a < b ? a : b, hi = a < b ? b : a;
+  const float dx = vs[3 * (int64_t)hi] - vs[3 * (int64_t)lo];
+  const float dy = vs[3 * (int64_t)hi + 1] - vs[3 * (int64_t)lo + 1];
+  const float dz = vs[3 * (int64_t)hi + 2] - vs[3 * (int64_t)lo + 2];
+  return dx * dx + dy * dy + dz * dz;
+}
+
+// ---- the caller's input -------------------------------------------------------------------------------------------------
+__global__ void reset_counters(unsigned long long* __restrict__ ctr) {
+  const int i = threadIdx.x;
+  if (i < kCounters) ctr[i] = (i == kBadFace || i == kBadVertex || i == kBadKey) ? ~0ull : 0ull;
+}
+
+// tri = the faces as int32 (zeros where an id is out of range); counts repeated vertices
+__global__ void classify_faces(const int64_t* __restrict__ faces, int64_t F, int64_t V, int32_t* __restrict__ tri,
+                               unsigned long long* __restrict__ ctr) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= F) return;
+  int64_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
+  if (a < 0 || a >= V || b < 0 || b >= V || c < 0 || c >= V) {
+    ctr[kOutOfRange] = 1;
+    a = b = c = 0;
+  } else if (a == b || b == c || c == a) {
+    atomicAdd(&ctr[kDegenerate], 1ull);
+    atomicMin(&ctr[kBadFace], (unsigned long long)f);
+  }
+  tri[3 * f] = (int32_t)a;
+  tri[3 * f + 1] = (int32_t)b;
+  tri[3 * f + 2] = (int32_t)c;
+}
+
+__global__ void check_vertices(const float* __restrict__ vs, int64_t V, int32_t* __restrict__ par,
+                               unsigned long long* __restrict__ ctr) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  if (!(isfinite(vs[3 * v]) && isfinite(vs[3 * v + 1]) && isfinite(vs[3 * v + 2]))) {
+    atomicAdd(&ctr[kNonFinite], 1ull);
+    atomicMin(&ctr[kBadVertex], (unsigned long long)v);
+  }
+  par[2 * v] = par[2 * v + 1] = (int32_t)v;
+}
+
+// ---- analysis -------------------------------------------------------------------------------------------------------------
+__global__ void half_edge_keys(const int32_t* __restrict__ tri, int64_t n_half, int64_t V, uint64_t* __restrict__ keys,
+                               int32_t* __restrict__ vals) {
+  const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (h >= n_half) return;
+  const int64_t f = h / 3;
+  const int k = (int)(h - 3 * f);
+  const int64_t a = tri[h], b = tri[3 * f + next3(k)];
+  keys[h] = (uint64_t)(a < b ? a : b) * (uint64_t)V + (uint64_t)(a < b ? b : a);
+  vals[h] = (int32_t)h;
+}
+
+__global__ void mark_heads(const uint64_t* __restrict__ keys, int64_t n, int32_t* __restrict__ head) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  head[p] = (p == 0 || keys[p] != keys[p - 1]) ? 1 : 0;
+}
+
+// faces of the run that starts at the head p (3 stands for "three or more")
+__device__ inline int run_length(const int32_t* __restrict__ head, int64_t p, int64_t n) {
+  if (p + 1 >= n || head[p + 1]) return 1;
+  if (p + 2 >= n || head[p + 2]) return 2;
+  return 3;
+}
+
+// he_rank[h] = rank of h's edge; per edge: the validation counts, border vertices and (val != null) the valences
+__global__ void edge_pass(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals, const int32_t* __restrict__ head,
+                          const int32_t* __restrict__ incl, int64_t n, int64_t F, int64_t V, const int32_t* __restrict__ tri,
+                          int32_t* __restrict__ he_rank, uint8_t* __restrict__ border, int32_t* __restrict__ val,
+                          unsigned long long* __restrict__ ctr) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const int32_t h = vals[p];
+  if (h < 0 || h >= n) return;
+  he_rank[h] = incl[p] - 1;
+  if (!head[p]) return;
+  const int64_t f = h / 3;
+  const int k = (int)(h - 3 * f);
+  const int32_t a = tri[h], b = tri[3 * f + next3(k)];
+  if (a < 0 || a >= V || b < 0 || b >= V) return;
+  atomicAdd(&ctr[kEdges], 1ull);
+  if (val) {
+    atomicAdd(val + a, 1);
+    atomicAdd(val + b, 1);
+  }
+  const int len = run_length(head, p, n);
+  if (len == 1) {
+    atomicAdd(&ctr[kBorderEdges], 1ull);
+    border[a] = 1;                                   // every writer stores the same 1
+    border[b] = 1;
+  } else if (len == 2) {
+    const int32_t h1 = vals[p + 1];
+    if (h1 >= 0 && h1 < n && tri[h1] == a) {         // both faces run the edge from a: not opposite
+      atomicAdd(&ctr[kMisoriented], 1ull);
+      atomicMin(&ctr[kBadKey], (unsigned long long)keys[p]);
+    }
+  } else {
+    atomicAdd(&ctr[kNonManifold], 1ull);
+    atomicMin(&ctr[kBadKey], (unsigned long long)keys[p]);
+  }
+}
+
+// ---- split ----------------------------------------------------------------------------------------------------------------
+// best[f] = the rank of f's long edge of highest priority, -1 when f has no long edge
+__global__ void face_best_edge(const int32_t* __restrict__ tri, const int32_t* __restrict__ he_rank, const float* __restrict__ vs,
+                               int64_t F, float thr2, int32_t* __restrict__ best) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= F) return;
+  int32_t v[3] = {tri[3 * f], tri[3 * f + 1], tri[3 * f + 2]};
+  int32_t b = -1;
+  uint64_t bp = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float l2 = edge_len2(vs, v[k], v[next3(k)]);
+    if (!(l2 > thr2)) continue;
+    const int32_t r = he_rank[3 * f + k];
+    const uint64_t pr = ((uint64_t)__float_as_uint(l2) << 32) | hash32((uint32_t)r);
+    if (b < 0 || pr > bp) {
+      b = r;
+      bp = pr;
+    }
+  }
+  best[f] = b;
+}
+
+// flag_a[p] = 1 at the head of a selected edge (entry n is 0); its faces get flag_f = 1 and fpos = p
+__global__ void select_split(const int32_t* __restrict__ vals, const int32_t* __restrict__ head, const int32_t* __restrict__ incl,
+                             int64_t n, int64_t F, const int32_t* __restrict__ tri, const float* __restrict__ vs, float thr2,
+                             const int32_t* __restrict__ best, int32_t* __restrict__ flag_a, int32_t* __restrict__ flag_f,
+                             int32_t* __restrict__ fpos, unsigned long long* __restrict__ ctr) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p > n) return;
+  int32_t sel = 0;
+  if (p < n && head[p]) {
+    const int32_t h = vals[p];
+    const int64_t f = h / 3;
+    const int k = (int)(h - 3 * f);
+    if (edge_len2(vs, tri[h], tri[3 * f + next3(k)]) > thr2) {
+      atomicAdd(&ctr[kLong], 1ull);
+      const int32_t r = incl[p] - 1;
+      const int len = run_length(head, p, n);        // 1 or 2: the mesh was validated
+      const int64_t f1 = len == 2 ? vals[p + 1] / 3 : f;
+      if (best[f] == r && best[f1] == r && f1 < F) {
+        sel = 1;
+        flag_f[f] = 1;
+        fpos[f] = (int32_t)p;
+        flag_f[f1] = 1;
+        fpos[f1] = (int32_t)p;
+      }
+    }
+  }
+  flag_a[p] = sel;
+}
+
+__global__ void store_totals(const int32_t* __restrict__ scan_a, int64_t n, const int32_t* __restrict__ scan_f, int64_t F,
+                             unsigned long long* __restrict__ ctr) {
+  ctr[kTotalA] = (unsigned long long)scan_a[n];
+  ctr[kTotalF] = (unsigned long long)scan_f[F];
+}
+
+// vertex V + s of the s-th selected edge: the midpoint, its two ends, and whether it lies on the border
+__global__ void emit_split_vertices(const int32_t* __restrict__ vals, const int32_t* __restrict__ head,
+                                    const int32_t* __restrict__ flag_a, const int32_t* __restrict__ scan_a, int64_t n, int64_t V,
+                                    int64_t S, const int32_t* __restrict__ tri, float* __restrict__ vs, int32_t* __restrict__ par,
+                                    uint8_t* __restrict__ border) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n || !flag_a[p]) return;
+  const int64_t s = scan_a[p];
+  if (s < 0 || s >= S) return;
+  const int32_t h = vals[p];
+  const int64_t f = h / 3;
+  const int k = (int)(h - 3 * f);
+  const int32_t a = tri[h], b = tri[3 * f + next3(k)];
+  const int64_t lo = a < b ? a : b, hi = a < b ? b : a, m = V + s;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) vs[3 * m + i] = (vs[3 * lo + i] + vs[3 * hi + i]) * kHalf;
+  par[2 * m] = (int32_t)lo;
+  par[2 * m + 1] = (int32_t)hi;
+  border[m] = run_length(head, p, n) == 1 ? 1 : 0;
+}
+
+// (a, b, c) with the selected edge from a to b: (a, m, c) stays in slot f, (m, b, c) goes to slot F + t
+__global__ void emit_split_faces(const int32_t* __restrict__ flag_f, const int32_t* __restrict__ scan_f,
+                                 const int32_t* __restrict__ fpos, const int32_t* __restrict__ scan_a,
+                                 const int32_t* __restrict__ he_rank, const int32_t* __restrict__ best, int64_t F, int64_t V,
+                                 int64_t S, int64_t T, int64_t n, int32_t* __restrict__ tri) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= F || !flag_f[f]) return;
+  const int64_t t = scan_f[f], p = fpos[f];
+  if (t < 0 || t >= T || p < 0 || p >= n) return;
+  const int64_t s = scan_a[p];
+  if (s < 0 || s >= S) return;
+  const int32_t r = best[f];
+  const int k = he_rank[3 * f] == r ? 0 : (he_rank[3 * f + 1] == r ? 1 : 2);
+  const int32_t a = tri[3 * f + k], b = tri[3 * f + next3(k)], c = tri[3 * f + next3(next3(k))], m = (int32_t)(V + s);
+  tri[3 * f] = a;
+  tri[3 * f + 1] = m;
+  tri[3 * f + 2] = c;
+  const int64_t g = F + t;
+  tri[3 * g] = m;
+  tri[3 * g + 1] = b;
+  tri[3 * g + 2] = c;
+}
+
+// ---- flip -----------------------------------------------------------------------------------------------------------------
+__device__ inline int target_valence(const uint8_t* __restrict__ border, int32_t v) { return border[v] ? 4 : 6; }
+
+__device__ inline int iabs(int x) { return x < 0 ? -x : x; }
+
+// sum over the vertices with an edge of |valence - target|
+__global__ void valence_deviation(const int32_t* __restrict__ val, const uint8_t* __restrict__ border, int64_t V,
+                                  unsigned long long* __restrict__ ctr) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int d = 0;
+  if (v < V && val[v] > 0) d = iabs(val[v] - target_valence(border, (int32_t)v));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) d += __shfl_down(d, off, 64);
+  if ((threadIdx.x & 63) == 0 && d > 0) atomicAdd(&ctr[kDeviation], (unsigned long long)d);
+}
+
+struct D3 {
+  double x, y, z;
+};
+__device__ inline D3 sub3(const float* __restrict__ vs, int32_t p, int32_t q) {      // vs[p] - vs[q] in float64
+  return {(double)vs[3 * (int64_t)p] - (double)vs[3 * (int64_t)q], (double)vs[3 * (int64_t)p + 1] - (double)vs[3 * (int64_t)q + 1],
+          (double)vs[3 * (int64_t)p + 2] - (double)vs[3 * (int64_t)q + 2]};
+}
+__device__ inline D3 cross3(const D3& u, const D3& v) {
+  return {u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x};
+}
+__device__ inline double dot3(const D3& u, const D3& v) { return u.x * v.x + u.y * v.y + u.z * v.z; }
+
+// the four vertices of the interior edge whose run starts at p: (a, b, c) is the face of the lower half-edge, (b, a, d) the other
+__device__ inline void flip_quad(const int32_t* __restrict__ vals, const int32_t* __restrict__ tri, int64_t p, int32_t q[4]) {
+  const int32_t h0 = vals[p], h1 = vals[p + 1];
+  const int64_t f0 = h0 / 3, f1 = h1 / 3;
+  const int k0 = (int)(h0 - 3 * f0), k1 = (int)(h1 - 3 * f1);
+  q[0] = tri[h0];
+  q[1] = tri[3 * f0 + next3(k0)];
+  q[2] = tri[3 * f0 + next3(next3(k0))];
+  q[3] = tri[3 * f1 + next3(next3(k1))];
+}
+
+// cand[p] = gain << 32 | hash(rank) for a candidate, 0 otherwise; every candidate bids for its four vertices
+__global__ void flip_candidates(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals, const int32_t* __restrict__ head,
+                                const int32_t* __restrict__ incl, int64_t n, int64_t V, const int32_t* __restrict__ tri,
+                                const float* __restrict__ vs, const int32_t* __restrict__ val, const uint8_t* __restrict__ border,
+                                unsigned long long* __restrict__ cand, unsigned long long* __restrict__ slot) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  unsigned long long key = 0;
+  if (head[p] && run_length(head, p, n) == 2) {
+    int32_t q[4];
+    flip_quad(vals, tri, p, q);
+    const int32_t a = q[0], b = q[1], c = q[2], d = q[3];
+    bool ok = c != d;
+    if (ok) {                                        // {c, d} must not be an edge yet: lower bound in the sorted keys
+      const uint64_t want = (uint64_t)(c < d ? c : d) * (uint64_t)V + (uint64_t)(c < d ? d : c);
+      int64_t lo = 0, hi = n;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (keys[mid] < want) lo = mid + 1;
+        else hi = mid;
+      }
+      ok = !(lo < n && keys[lo] == want);
+    }
+    int gain = 0;
+    if (ok) {
+      const int va = val[a], vb = val[b], vc = val[c], vd = val[d];
+      const int ta = target_valence(border, a), tb = target_valence(border, b), tc = target_valence(border, c),
+                td = target_valence(border, d);
+      ok = va - 1 >= (border[a] ? 2 : 3) && vb - 1 >= (border[b] ? 2 : 3);
+      gain = (iabs(va - ta) + iabs(vb - tb) + iabs(vc - tc) + iabs(vd - td)) -
+             (iabs(va - 1 - ta) + iabs(vb - 1 - tb) + iabs(vc + 1 - tc) + iabs(vd + 1 - td));
+      ok = ok && gain > 0;
+    }
+    if (ok) {                                        // the guard: both new normals on the side of both old ones
+      const D3 o1 = cross3(sub3(vs, b, a), sub3(vs, c, a)), o2 = cross3(sub3(vs, a, b), sub3(vs, d, b));
+      const D3 n1 = cross3(sub3(vs, d, a), sub3(vs, c, a)), n2 = cross3(sub3(vs, b, d), sub3(vs, c, d));
+      ok = dot3(n1, o1) > 0.0 && dot3(n1, o2) > 0.0 && dot3(n2, o1) > 0.0 && dot3(n2, o2) > 0.0;
+    }
+    if (ok) {
+      key = ((unsigned long long)gain << 32) | hash32((uint32_t)(incl[p] - 1));
+      atomicMax(slot + a, key);
+      atomicMax(slot + b, key);
+      atomicMax(slot + c, key);
+      atomicMax(slot + d, key);
+    }
+  }
+  cand[p] = key;
+}
+
+__global__ void flip_check(const unsigned long long* __restrict__ cand, const int32_t* __restrict__ vals,
+                           const int32_t* __restrict__ tri, const unsigned long long* __restrict__ slot, int64_t n,
+                           uint8_t* __restrict__ win, unsigned long long* __restrict__ ctr) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const unsigned long long key = cand[p];
+  uint8_t w = 0;
+  if (key) {
+    int32_t q[4];
+    flip_quad(vals, tri, p, q);
+    w = (slot[q[0]] == key && slot[q[1]] == key && slot[q[2]] == key && slot[q[3]] == key) ? 1 : 0;
+    if (w) atomicAdd(&ctr[kWinners], 1ull);
+  }
+  win[p] = w;
+}
+
+// (a, d, c) into the slot of (a, b, c), (d, b, c) into the slot of (b, a, d)
+__global__ void flip_apply(const uint8_t* __restrict__ win, const int32_t* __restrict__ vals, int64_t n, int32_t* __restrict__ tri) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n || !win[p]) return;
+  int32_t q[4];
+  flip_quad(vals, tri, p, q);
+  const int64_t f0 = vals[p] / 3, f1 = vals[p + 1] / 3;
+  tri[3 * f0] = q[0];
+  tri[3 * f0 + 1] = q[3];
+  tri[3 * f0 + 2] = q[2];
+  tri[3 * f1] = q[3];
+  tri[3 * f1 + 1] = q[1];
+  tri[3 * f1 + 2] = q[2];
+}
+
+// ---- export -----------------------------------------------------------------------------------------------------------------
+__global__ void widen32(const int32_t* __restrict__ in, int64_t n, int64_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = in[i];
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------------
+inline unsigned long long* ctr_of(sg_remesh* s) { return (unsigned long long*)s->ctr.p; }
+
+int sort_bits(int64_t V) {                           // the keys are below V * V < 2^62
+  int bits = 1;
+  while (bits < 62 && (((uint64_t)V * (uint64_t)V) >> bits) != 0) ++bits;
+  return bits;
+}
+
+// keys, sort, heads, ranks, edge pass on the mesh as it stands; resets the counters first.  No host synchronisation unless a
+// scratch buffer has to grow.
+int analyse(sg_remesh* s, bool with_valence, hipStream_t stream) {
+  const int64_t V = s->V, F = s->F, n = 3 * F;
+  for (Buf* b : {&s->keys_a, &s->keys_b, &s->cand})
+    if (int rc = reserve(b, (size_t)n * sizeof(uint64_t), false, stream)) return rc;
+  for (Buf* b : {&s->vals_a, &s->vals_b, &s->head, &s->incl, &s->he_rank})
+    if (int rc = reserve(b, (size_t)n * sizeof(int32_t), false, stream)) return rc;
+  for (Buf* b : {&s->flag_a, &s->scan_a})
+    if (int rc = reserve(b, (size_t)(n + 1) * sizeof(int32_t), false, stream)) return rc;
+  for (Buf* b : {&s->flag_f, &s->scan_f, &s->best, &s->fpos})
+    if (int rc = reserve(b, (size_t)(F + 1) * sizeof(int32_t), false, stream)) return rc;
+  if (int rc = reserve(&s->win, (size_t)n, false, stream)) return rc;
+  if (int rc = reserve(&s->slot, (size_t)V * sizeof(uint64_t), false, stream)) return rc;
+  if (int rc = reserve(&s->val, (size_t)V * sizeof(int32_t), false, stream)) return rc;
+  const int bits = sort_bits(V);
+  size_t tb_sort = 0, tb_incl = 0, tb_a = 0, tb_f = 0;
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, (const uint64_t*)s->keys_a.p, (uint64_t*)s->keys_b.p,
+                                                (const int32_t*)s->vals_a.p, (int32_t*)s->vals_b.p, (int)n, 0, bits, stream));
+  SG_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb_incl, (const int32_t*)s->head.p, (int32_t*)s->incl.p, (int)n, stream));
+  SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_a, (const int32_t*)s->flag_a.p, (int32_t*)s->scan_a.p, (int)(n + 1), stream));
+  SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_f, (const int32_t*)s->flag_f.p, (int32_t*)s->scan_f.p, (int)(F + 1), stream));
+  size_t tb = tb_sort;
+  for (size_t t : {tb_incl, tb_a, tb_f}) tb = t > tb ? t : tb;
+  if (int rc = reserve(&s->temp, tb ? tb : 16, false, stream)) return rc;
+
+  reset_counters<<<1, 64, 0, stream>>>(ctr_of(s));
+  SG_HIP_TRY(hipMemsetAsync(s->border.p, 0, (size_t)V, stream));
+  if (with_valence) SG_HIP_TRY(hipMemsetAsync(s->val.p, 0, (size_t)V * sizeof(int32_t), stream));
+  half_edge_keys<<<blocks_for(n), kThreads, 0, stream>>>((const int32_t*)s->tri.p, n, V, (uint64_t*)s->keys_a.p, (int32_t*)s->vals_a.p);
+  SG_HIP_TRY(hipGetLastError());
+  size_t tb_use = s->temp.cap;
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(s->temp.p, tb_use, (const uint64_t*)s->keys_a.p, (uint64_t*)s->keys_b.p,
+                                                (const int32_t*)s->vals_a.p, (int32_t*)s->vals_b.p, (int)n, 0, bits, stream));
+  mark_heads<<<blocks_for(n), kThreads, 0, stream>>>((const uint64_t*)s->keys_b.p, n, (int32_t*)s->head.p);
+  SG_HIP_TRY(hipGetLastError());
+  tb_use = s->temp.cap;
+  SG_HIP_TRY(hipcub::DeviceScan::InclusiveSum(s->temp.p, tb_use, (const int32_t*)s->head.p, (int32_t*)s->incl.p, (int)n, stream));
+  edge_pass<<<blocks_for(n), kThreads, 0, stream>>>((const uint64_t*)s->keys_b.p, (const int32_t*)s->vals_b.p,
+                                                   (const int32_t*)s->head.p, (const int32_t*)s->incl.p, n, F, V,
+                                                   (const int32_t*)s->tri.p, (int32_t*)s->he_rank.p, (uint8_t*)s->border.p,
+                                                   with_valence ? (int32_t*)s->val.p : nullptr, ctr_of(s));
+  SG_HIP_TRY(hipGetLastError());
+  return SG_OK;
+}
+
+int read_counters(sg_remesh* s, unsigned long long* h, hipStream_t stream) {
+  SG_HIP_TRY(hipMemcpyAsync(h, s->ctr.p, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipStreamSynchronize(stream));
+  return SG_OK;
+}
+
+}  // namespace
+
+void destroy_remesh(sg_remesh* s) {
+  if (!s) return;
+  for (Buf* b : {&s->vs, &s->par, &s->tri, &s->border, &s->keys_a, &s->keys_b, &s->vals_a, &s->vals_b, &s->head, &s->incl,
+                 &s->he_rank, &s->best, &s->fpos, &s->flag_a, &s->scan_a, &s->flag_f, &s->scan_f, &s->cand, &s->win, &s->slot,
+                 &s->val, &s->temp, &s->ctr})
+    if (b->p) (void)hipFree(b->p);
+  delete s;
+}
+
+int remesh_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, hipStream_t stream, sg_remesh** out) {
+  SG_REQUIRE(V < ((int64_t)1 << 31) && 3 * F < ((int64_t)1 << 31), "sg_remesh_create: sizes must fit int32");
+  sg_remesh* s = new (std::nothrow) sg_remesh;
+  SG_REQUIRE(s != nullptr, "sg_remesh_create: out of host memory");
+  struct Guard {
+    sg_remesh* s;
+    ~Guard() { destroy_remesh(s); }
+  } guard{s};
+  s->V = s->V0 = V;
+  s->F = s->F0 = F;
+  s->h_ctr[kBadFace] = s->h_ctr[kBadVertex] = s->h_ctr[kBadKey] = ~0ull;
+  s->bad_key_V = V;
+  if (V == 0) {
+    SG_REQUIRE(F == 0, "sg_remesh_create: face refers to a vertex outside [0, 0)");
+    s->valid = true;
+    guard.s = nullptr;
+    *out = s;
+    return SG_OK;
+  }
+  if (int rc = reserve(&s->ctr, kCounters * sizeof(unsigned long long), false, stream)) return rc;
+  if (int rc = reserve(&s->vs, (size_t)V * 3 * sizeof(float), false, stream)) return rc;
+  if (int rc = reserve(&s->par, (size_t)V * 2 * sizeof(int32_t), false, stream)) return rc;
+  if (int rc = reserve(&s->border, (size_t)V, false, stream)) return rc;
+  if (int rc = reserve(&s->tri, (size_t)F * 3 * sizeof(int32_t), false, stream)) return rc;
+  SG_HIP_TRY(hipMemcpyAsync(s->vs.p, vs, (size_t)V * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
+  SG_HIP_TRY(hipMemsetAsync(s->border.p, 0, (size_t)V, stream));
+  reset_counters<<<1, 64, 0, stream>>>(ctr_of(s));
+  if (F > 0) classify_faces<<<blocks_for(F), kThreads, 0, stream>>>(faces, F, V, (int32_t*)s->tri.p, ctr_of(s));
+  check_vertices<<<blocks_for(V), kThreads, 0, stream>>>((const float*)s->vs.p, V, (int32_t*)s->par.p, ctr_of(s));
+  SG_HIP_TRY(hipGetLastError());
+  unsigned long long first[kCounters];
+  if (int rc = read_counters(s, first, stream)) return rc;
+  SG_REQUIRE(!first[kOutOfRange], "sg_remesh_create: face refers to a vertex outside [0, %lld)", (long long)V);
+  if (F > 0) {
+    if (int rc = analyse(s, false, stream)) return rc;   // resets the counters: the face and vertex counts are kept in `first`
+    if (int rc = read_counters(s, s->h_ctr, stream)) return rc;
+  }
+  for (int i : {(int)kDegenerate, (int)kBadFace, (int)kNonFinite, (int)kBadVertex}) s->h_ctr[i] = first[i];
+  s->valid = !s->h_ctr[kDegenerate] && !s->h_ctr[kNonFinite] && !s->h_ctr[kNonManifold] && !s->h_ctr[kMisoriented];
+  guard.s = nullptr;
+  *out = s;
+  return SG_OK;
+}
+
+void remesh_query(const sg_remesh* s, int64_t* info) {
+  const unsigned long long* c = s->h_ctr;
+  const bool bad_edge = c[kBadKey] != ~0ull && s->bad_key_V > 0;
+  info[0] = s->V;
+  info[1] = s->F;
+  info[2] = (int64_t)c[kEdges];
+  info[3] = (int64_t)c[kBorderEdges];
+  info[4] = (int64_t)c[kNonManifold];
+  info[5] = (int64_t)c[kMisoriented];
+  info[6] = (int64_t)c[kDegenerate];
+  info[7] = (int64_t)c[kNonFinite];
+  info[8] = bad_edge ? (int64_t)(c[kBadKey] / (unsigned long long)s->bad_key_V) : -1;
+  info[9] = bad_edge ? (int64_t)(c[kBadKey] % (unsigned long long)s->bad_key_V) : -1;
+  info[10] = c[kBadFace] != ~0ull ? (int64_t)c[kBadFace] : -1;
+  info[11] = c[kBadVertex] != ~0ull ? (int64_t)c[kBadVertex] : -1;
+  info[12] = s->V0;
+  info[13] = s->F0;
+  info[14] = s->valid ? 1 : 0;
+  info[15] = 0;
+}
+
+int remesh_split(sg_remesh* s, float thr2, int64_t max_rounds, hipStream_t stream, int64_t* counts, int64_t* n_rounds,
+                 int64_t* n_long) {
+  *n_rounds = 0;
+  *n_long = 0;
+  SG_REQUIRE(s->valid, "sg_remesh_split: the mesh did not pass validation (sg_remesh_query)");
+  if (s->F == 0) return SG_OK;
+  for (int64_t round = 0;; ++round) {
+    const int64_t V = s->V, F = s->F, n = 3 * F;
+    if (int rc = analyse(s, false, stream)) return rc;
+    face_best_edge<<<blocks_for(F), kThreads, 0, stream>>>((const int32_t*)s->tri.p, (const int32_t*)s->he_rank.p,
+                                                          (const float*)s->vs.p, F, thr2, (int32_t*)s->best.p);
+    SG_HIP_TRY(hipMemsetAsync(s->flag_f.p, 0, (size_t)(F + 1) * sizeof(int32_t), stream));
+    select_split<<<blocks_for(n + 1), kThreads, 0, stream>>>((const int32_t*)s->vals_b.p, (const int32_t*)s->head.p,
+                                                            (const int32_t*)s->incl.p, n, F, (const int32_t*)s->tri.p,
+                                                            (const float*)s->vs.p, thr2, (const int32_t*)s->best.p,
+                                                            (int32_t*)s->flag_a.p, (int32_t*)s->flag_f.p, (int32_t*)s->fpos.p,
+                                                            ctr_of(s));
+    SG_HIP_TRY(hipGetLastError());
+    size_t tb = s->temp.cap;
+    SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->temp.p, tb, (const int32_t*)s->flag_a.p, (int32_t*)s->scan_a.p, (int)(n + 1), stream));
+    tb = s->temp.cap;
+    SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->temp.p, tb, (const int32_t*)s->flag_f.p, (int32_t*)s->scan_f.p, (int)(F + 1), stream));
+    store_totals<<<1, 1, 0, stream>>>((const int32_t*)s->scan_a.p, n, (const int32_t*)s->scan_f.p, F, ctr_of(s));
+    SG_HIP_TRY(hipGetLastError());
+    unsigned long long c[kCounters];
+    if (int rc = read_counters(s, c, stream)) return rc;       // the round's one synchronisation: count -> emit
+    const int64_t S = (int64_t)c[kTotalA], T = (int64_t)c[kTotalF];
+    *n_long = (int64_t)c[kLong];
+    SG_REQUIRE(S >= 0 && S <= n && T >= S && T <= 2 * S && T <= F, "sg_remesh_split: totals out of range (%lld edges, %lld faces)",
+               (long long)S, (long long)T);
+    if (S == 0 || round >= max_rounds) break;
+    SG_REQUIRE(V + S < ((int64_t)1 << 31) && 3 * (F + T) < ((int64_t)1 << 31), "sg_remesh_split: sizes must fit int32");
+    if (int rc = reserve(&s->vs, (size_t)(V + S) * 3 * sizeof(float), true, stream)) return rc;
+    if (int rc = reserve(&s->par, (size_t)(V + S) * 2 * sizeof(int32_t), true, stream)) return rc;
+    if (int rc = reserve(&s->border, (size_t)(V + S), true, stream)) return rc;
+    if (int rc = reserve(&s->tri, (size_t)(F + T) * 3 * sizeof(int32_t), true, stream)) return rc;
+    emit_split_vertices<<<blocks_for(n), kThreads, 0, stream>>>((const int32_t*)s->vals_b.p, (const int32_t*)s->head.p,
+                                                               (const int32_t*)s->flag_a.p, (const int32_t*)s->scan_a.p, n, V, S,
+                                                               (const int32_t*)s->tri.p, (float*)s->vs.p, (int32_t*)s->par.p,
+                                                               (uint8_t*)s->border.p);
+    emit_split_faces<<<blocks_for(F), kThreads, 0, stream>>>((const int32_t*)s->flag_f.p, (const int32_t*)s->scan_f.p,
+                                                            (const int32_t*)s->fpos.p, (const int32_t*)s->scan_a.p,
+                                                            (const int32_t*)s->he_rank.p, (const int32_t*)s->best.p, F, V, S, T, n,
+                                                            (int32_t*)s->tri.p);
+    SG_HIP_TRY(hipGetLastError());
+    s->V = V + S;
+    s->F = F + T;
+    counts[round] = S;
+    *n_rounds = round + 1;
+  }
+  return SG_OK;
+}
+
+int remesh_flip(sg_remesh* s, int64_t max_rounds, hipStream_t stream, int64_t* counts, int64_t* n_rounds, int64_t* deviation) {
+  *n_rounds = 0;
+  deviation[0] = deviation[1] = 0;
+  SG_REQUIRE(s->valid, "sg_remesh_flip: the mesh did not pass validation (sg_remesh_query)");
+  if (s->F == 0) return SG_OK;
+  const int64_t V = s->V, F = s->F, n = 3 * F;
+  for (int64_t round = 0;; ++round) {
+    if (int rc = analyse(s, true, stream)) return rc;
+    SG_HIP_TRY(hipMemsetAsync(s->slot.p, 0, (size_t)V * sizeof(uint64_t), stream));
+    valence_deviation<<<blocks_for(V), kThreads, 0, stream>>>((const int32_t*)s->val.p, (const uint8_t*)s->border.p, V, ctr_of(s));
+    flip_candidates<<<blocks_for(n), kThreads, 0, stream>>>((const uint64_t*)s->keys_b.p, (const int32_t*)s->vals_b.p,
+                                                           (const int32_t*)s->head.p, (const int32_t*)s->incl.p, n, V,
+                                                           (const int32_t*)s->tri.p, (const float*)s->vs.p, (const int32_t*)s->val.p,
+                                                           (const uint8_t*)s->border.p, (unsigned long long*)s->cand.p,
+                                                           (unsigned long long*)s->slot.p);
+    flip_check<<<blocks_for(n), kThreads, 0, stream>>>((const unsigned long long*)s->cand.p, (const int32_t*)s->vals_b.p,
+                                                      (const int32_t*)s->tri.p, (const unsigned long long*)s->slot.p, n,
+                                                      (uint8_t*)s->win.p, ctr_of(s));
+    SG_HIP_TRY(hipGetLastError());
+    unsigned long long c[kCounters];
+    if (int rc = read_counters(s, c, stream)) return rc;       // the round's one synchronisation: count -> apply
+    const int64_t W = (int64_t)c[kWinners];
+    if (round == 0) deviation[0] = (int64_t)c[kDeviation];
+    deviation[1] = (int64_t)c[kDeviation];
+    SG_REQUIRE(W >= 0 && W <= n, "sg_remesh_flip: winner count %lld out of range", (long long)W);
+    if (W == 0 || round >= max_rounds) break;
+    flip_apply<<<blocks_for(n), kThreads, 0, stream>>>((const uint8_t*)s->win.p, (const int32_t*)s->vals_b.p, n, (int32_t*)s->tri.p);
+    SG_HIP_TRY(hipGetLastError());
+    counts[round] = W;
+    *n_rounds = round + 1;
+  }
+  return SG_OK;
+}
+
+int remesh_export(const sg_remesh* s, float* vs, int64_t* faces, int64_t* parents, uint8_t* border, hipStream_t stream) {
+  const int64_t V = s->V, F = s->F;
+  SG_REQUIRE((V == 0 || (vs && parents)) && (F == 0 || faces), "sg_remesh_export: null pointer");
+  if (V == 0 && F == 0) return SG_OK;               // nothing to write, no device to ask
+  if (V > 0) {
+    SG_HIP_TRY(hipMemcpyAsync(vs, s->vs.p, (size_t)V * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    widen32<<<blocks_for(2 * V), kThreads, 0, stream>>>((const int32_t*)s->par.p, 2 * V, parents);
+    if (border) SG_HIP_TRY(hipMemcpyAsync(border, s->border.p, (size_t)V, hipMemcpyDeviceToDevice, stream));
+  }
+  if (F > 0) widen32<<<blocks_for(3 * F), kThreads, 0, stream>>>((const int32_t*)s->tri.p, 3 * F, faces);
+  SG_HIP_TRY(hipGetLastError());
+  return SG_OK;
+}
+
+}  // namespace sg

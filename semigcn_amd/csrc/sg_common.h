@@ -390,6 +390,14 @@ int parts_labels(const sg_parts* s, int64_t* face_label, int64_t* face_count, hi
 int parts_select(sg_parts* s, const uint8_t* keep, hipStream_t stream, int64_t* n_vertices, int64_t* n_faces);
 int parts_emit(sg_parts* s, const float* vs, float* new_vs, int64_t* new_faces, int64_t* vertex_ids, int64_t* face_ids,
                hipStream_t stream);
+// mesh_remesh.hip
+int remesh_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, hipStream_t stream, sg_remesh** out);
+void destroy_remesh(sg_remesh* s);
+void remesh_query(const sg_remesh* s, int64_t* info);
+int remesh_split(sg_remesh* s, float thr2, int64_t max_rounds, hipStream_t stream, int64_t* counts, int64_t* n_rounds,
+                 int64_t* n_long);
+int remesh_flip(sg_remesh* s, int64_t max_rounds, hipStream_t stream, int64_t* counts, int64_t* n_rounds, int64_t* deviation);
+int remesh_export(const sg_remesh* s, float* vs, int64_t* faces, int64_t* parents, uint8_t* border, hipStream_t stream);
 
 // trace.hip -- optional per-launch event timing (sg_trace_*)
 extern std::atomic<bool> g_trace_on;

@@ -1,0 +1,392 @@
+"""Refine a mesh to a target edge length on the device: split long edges, flip towards regular valence, relax and re-project.
+
+Replaces, apart from edge collapse, the isotropic remesh the reference runs between MeshFix and the scaling
+(preprocess/prepare.py:35-42: MeshLab's ``remeshing_isotropic_explicit_remeshing`` at 0.6 % of the box diagonal).  What
+the networks need from that step is a uniform edge length and valences near 6; ``holes.fill_holes`` patches at roughly
+the border's edge length, a ``-CAD`` input arrives with a few huge triangles, and ``meshprep.qem_contract`` only coarsens.
+**Edge collapse is not done here**: short edges stay and are only counted (``n_short``).  MeshLab is not available to
+compare against; the construction below is this module's own and is the specification the tests pin
+(tests/remesh_oracle.py restates it in numpy with serial, dictionary-based code).  The kernels are csrc/mesh_remesh.hip.
+
+**Input.**  ``(vs float32 [V, 3], faces int64 [F, 3])``, as ``repair.repair`` returns it.  Every undirected edge must have
+one face (a border edge) or two faces that run it in opposite directions.  ``ValueError`` is raised -- and nothing is done --
+when an edge has three or more faces, when the two faces of an edge run it in the same direction, when a face repeats a
+vertex or when a coordinate is not finite; the message gives the four counts and the smallest offending edge ``(lo, hi)``,
+face and vertex.
+
+**Edges.**  Half-edge ``h = 3 f + k`` of face ``f`` runs from ``faces[f, k]`` to ``faces[f, (k + 1) % 3]``.  The undirected
+edges in ascending ``(lo, hi)`` order have the ranks ``r = 0, 1, ...``.  ``hash(r)`` is the 32-bit mixer ``x ^= x >> 16;
+x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16`` (arithmetic modulo 2^32).  It is a bijection of the 32-bit
+integers, so the hashes of two edges never tie; it breaks the long tie chains of regular grids.
+
+**1. split_long_edges.**  A round works on the mesh it starts with.
+
+* ``len2 = dx * dx + dy * dy + dz * dz`` in float32, summed left to right, with ``d = vs[hi] - vs[lo]``.  An edge is *long*
+  when ``len2 > thr2``; ``thr2 = float32((4/3 target)^2)`` is formed once on the host in float64.
+* The priority of a long edge is the tuple (``len2`` as its bit pattern, ``hash(r)``, lower ``r``); the third component
+  never decides.  A long edge is *selected* when, in each of its faces, no other long edge has a higher priority.  A face
+  therefore has at most one selected edge, and the longest edge of the mesh is always selected.
+* Selected edges in ascending rank ``s = 0, 1, ...`` get vertex ``V + s`` at ``(vs[lo] + vs[hi]) * 0.5f`` per component,
+  with ``parents[V + s] = (lo, hi)``.  A face ``f`` whose corner ``k`` starts the selected edge, ``a = v_k, b = v_{k+1},
+  c = v_{k+2}``, becomes ``(a, m, c)`` in slot ``f`` and produces ``(m, b, c)`` in slot ``F + t``, ``t`` being its rank
+  among the split faces in ascending ``f``.  Orientation is preserved; the topology is integers only.
+* Rounds repeat until no edge is long or ``max_rounds`` rounds ran; running out of rounds is reported (``n_long > 0``),
+  not raised.  A long edge waits for every longer long edge of its two faces, so where the edge length falls steadily
+  along the surface (a regular grid under a smooth stretch, without noise) the rounds follow that slope one face at a time
+  and their number grows with its length; scans and jittered meshes break such chains after a few faces.  ``parents`` is ``(i, i)`` for a vertex of the input; the ends of an inserted vertex may be inserted ones.
+
+**2. flip_edges.**  ``val[v]`` is the number of distinct edges at ``v``; the target valence is 6, or 4 for a vertex on a
+border edge.  The *deviation* is the sum of ``|val - target|`` over the vertices that have an edge.
+
+* A candidate is an interior edge ``{a, b}`` with the face ``(a, b, c)`` on one side and ``(b, a, d)`` on the other; of its
+  two half-edges the one with the lower index ``h`` names ``a``, ``b`` and ``c``.  It needs ``c != d``; the edge ``{c, d}``
+  must be absent from the round's mesh; ``val[a] - 1`` and ``val[b] - 1`` must not fall below 3 (2 for a border vertex);
+  the *gain* -- the sum over ``a, b, c, d`` of ``|val - target|`` before, minus the same with ``a, b`` one lower and
+  ``c, d`` one higher -- must be positive; and the *guard* must hold: with ``n(p, q, r) = (q - p) x (r - p)`` in float64 from
+  the float32 coordinates, ``u x v = (u_y v_z - u_z v_y, u_z v_x - u_x v_z, u_x v_y - u_y v_x)`` and ``u . v = u_x v_x +
+  u_y v_y + u_z v_z`` summed left to right, the normals ``n(a, d, c)`` and ``n(d, b, c)`` of the new triangles each have a
+  strictly positive dot product with both ``n(a, b, c)`` and ``n(b, a, d)``.
+* The priority is (gain, ``hash(r)``, lower ``r``).  A candidate is *selected* when no other candidate whose vertex set
+  ``{a, b, c, d}`` meets its own has a higher priority.  Selected flips are vertex-disjoint.  ``(a, d, c)`` goes into the
+  slot of ``(a, b, c)``, ``(d, b, c)`` into the slot of ``(b, a, d)``.
+* Rounds repeat until none is selected or ``max_rounds`` rounds ran.  The deviation strictly falls every round.
+
+**3. relax_project.**  ``prepare.laplacian_smooth(..., steps, movable=interior vertices)``, then
+``evaluate.Surface.query`` on the moved vertices: the closest points become the positions.  Border vertices never move.
+
+**4. refine_mesh.**  ``target`` defaults to ``target_percent`` % of the input's box diagonal (MeshLab's ``Percentage``).
+The ``Surface`` is built once, from the input.  Each iteration is split (all rounds) -> flip -> relax_project.  Since
+relax_project moves vertices, it can push an edge back over 4/3 target; after the last iteration up to ``CLOSING_PASSES``
+closing passes therefore split again (all rounds) and project only the vertices they insert (border ones stay), until a
+pass finds no long edge: ``n_long == 0`` in the report then means that no edge of the RESULT has ``len2 > thr2``, exactly.
+The result is a valid ``initial`` for ``prepare.prepare_inputs``.  The report holds, per iteration, the split and flip counts per round,
+and for the result ``n_long`` (0 unless a cap ran out), ``n_short`` (edges below 4/5 target, which this stage does not
+treat), the min / mean / max edge length and the valence deviation at the start (the input) and the end.
+
+Nothing here uses a float atomic; integer maxima and sums do not depend on order, so every output is bit-reproducible.
+Inputs are what ``evaluate`` accepts; HIP device only: a CPU tensor raises ``SemigcnLibraryError``.
+
+Command line::
+
+    python -m semigcn_amd.remesh in.obj out.obj [--target X | --target-percent P] [--iterations N]
+    python -m semigcn_amd.remesh --torus NU NV --stretch S [--repeat R] [--target X | --target-percent P] [--iterations N]
+
+prints one JSON line with the sizes before and after, the rounds, the report and the device time of each stage
+(``surface_ms``, ``split_ms``, ``flip_ms``, ``relax_ms`` and ``report_ms``, summed over the iterations).  ``--torus NU NV --stretch S`` runs on
+``synth.torus_mesh(NU, NV)`` with x scaled by S.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import sys
+from dataclasses import dataclass
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from . import capi, prepare
+from .capi import RemeshPlan, SemigcnLibraryError
+from .evaluate import Surface, _vs_faces, read_obj
+
+__all__ = ["split_long_edges", "flip_edges", "relax_project", "refine_mesh", "Split", "Flipped", "Refined", "RemeshPlan",
+           "split_threshold", "CLOSING_PASSES"]
+
+#: refine_mesh: at most this many closing passes (split, project the inserted vertices) after the last iteration
+CLOSING_PASSES = 4
+
+
+@dataclass
+class Split:
+    """What ``split_long_edges`` returns.  The input's vertices are the prefix of ``vs``, bit-identical."""
+    vs: torch.Tensor            # float32 [V', 3]
+    faces: torch.Tensor         # int64 [F', 3]
+    parents: torch.Tensor       # int64 [V', 2]
+    counts: List[int]           # edges split per round
+    n_long: int                 # long edges left: 0 unless max_rounds ran out
+
+
+@dataclass
+class Flipped:
+    """What ``flip_edges`` returns; the positions are untouched."""
+    faces: torch.Tensor         # int64 [F, 3]
+    flips: List[int]            # flips per round
+    deviation_before: int
+    deviation_after: int
+
+
+@dataclass
+class Refined:
+    """What ``refine_mesh`` returns."""
+    vs: torch.Tensor            # float32 [V', 3]
+    faces: torch.Tensor         # int64 [F', 3]
+    parents: torch.Tensor       # int64 [V', 2]: (i, i) for a vertex of the input, the ends of the split edge otherwise
+    report: dict
+    stage_ms: Optional[dict] = None
+
+
+def split_threshold(target: float) -> float:
+    """``thr2 = float32((4/3 target)^2)``, formed in float64."""
+    return float(np.float32((4.0 / 3.0 * float(target)) ** 2))
+
+
+def _check_target(target, what="target"):
+    t = float(target)
+    if not (t > 0.0) or math.isinf(t):
+        raise ValueError(f"{what} must be a positive finite number, got {target}")
+    return t
+
+
+def _check_rounds(n, what):
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"{what} must be >= 0, got {n}")
+    return n
+
+
+def _check_mesh(mesh):
+    """Shapes and dtypes of a tensor / array mesh, before any device is asked for."""
+    if isinstance(mesh, (tuple, list)) and len(mesh) == 2:
+        vs, faces = mesh
+    elif hasattr(mesh, "vs") and hasattr(mesh, "faces"):
+        vs, faces = mesh.vs, mesh.faces
+    else:
+        raise TypeError("expected a mesh with .vs / .faces or a (vs, faces) pair")
+    for x, name, kinds in ((vs, "vs", "f"), (faces, "faces", "iu")):
+        shape = tuple(x.shape) if hasattr(x, "shape") else np.asarray(x).shape
+        if len(shape) != 2 or shape[1] != 3:
+            raise ValueError(f"{name} must be [N, 3], got {shape}")
+        if isinstance(x, torch.Tensor):
+            ok = x.dtype.is_floating_point if kinds == "f" else x.dtype in (torch.int64, torch.int32)
+        else:
+            ok = np.asarray(x).dtype.kind in kinds
+        if not ok:
+            raise ValueError(f"{name} must hold {'floats' if kinds == 'f' else 'integers'}, got {getattr(x, 'dtype', type(x))}")
+    return mesh
+
+
+def _plan(vs: torch.Tensor, faces: torch.Tensor) -> RemeshPlan:
+    plan = RemeshPlan(vs, faces)
+    if not plan.valid:
+        msg = (f"the mesh cannot be refined: {plan.n_nonmanifold} edge(s) with three or more faces, {plan.n_misoriented} "
+               f"edge(s) whose two faces run them in the same direction (smallest offending edge {plan.bad_edge}), "
+               f"{plan.n_degenerate} face(s) with a repeated vertex (smallest {plan.bad_face}), {plan.n_nonfinite} "
+               f"vertex/vertices with a non-finite coordinate (smallest {plan.bad_vertex})")
+        plan.close()
+        raise ValueError(msg)
+    return plan
+
+
+def split_long_edges(vs, faces, target: float, max_rounds: int = 64) -> Split:
+    """Split every edge longer than 4/3 ``target`` (module docstring, 1.)."""
+    target, max_rounds = _check_target(target), _check_rounds(max_rounds, "max_rounds")
+    _check_mesh((vs, faces))
+    vs, faces = _vs_faces(vs, faces)
+    with capi._on_device(vs.device):
+        plan = _plan(vs, faces)
+        try:
+            counts, n_long = plan.split(split_threshold(target), max_rounds)
+            out_vs, out_faces, parents, _ = plan.export()
+        finally:
+            torch.cuda.current_stream(vs.device).synchronize()     # the plan's buffers are freed with it
+            plan.close()
+    return Split(out_vs, out_faces, parents, counts, n_long)
+
+
+def flip_edges(vs, faces, max_rounds: int = 32) -> Flipped:
+    """Flip edges towards valence 6 (4 on the border) (module docstring, 2.)."""
+    max_rounds = _check_rounds(max_rounds, "max_rounds")
+    _check_mesh((vs, faces))
+    vs, faces = _vs_faces(vs, faces)
+    with capi._on_device(vs.device):
+        plan = _plan(vs, faces)
+        try:
+            flips, before, after = plan.flip(max_rounds)
+            _, out_faces, _, _ = plan.export()
+        finally:
+            torch.cuda.current_stream(vs.device).synchronize()
+            plan.close()
+    return Flipped(out_faces, flips, before, after)
+
+
+def _relax_project(vs, faces, border, surface: Surface, steps: int) -> torch.Tensor:
+    interior = ~border
+    moved = prepare.laplacian_smooth(vs, faces, steps=steps, movable=interior) if steps > 0 else vs
+    closest = surface.query(moved, signed=False)[2]
+    return torch.where(interior[:, None], closest, vs).contiguous()
+
+
+def relax_project(vs, faces, surface, steps: int = 1) -> torch.Tensor:
+    """``steps`` Laplacian steps on the interior vertices, then their closest points on ``surface`` (a ``Surface``, a mesh
+    object or a ``(vs, faces)`` pair) become the positions; border vertices never move (module docstring, 3.)."""
+    steps = _check_rounds(steps, "steps")
+    _check_mesh((vs, faces))
+    vs, faces = _vs_faces(vs, faces)
+    with capi._on_device(vs.device):
+        plan = _plan(vs, faces)
+        try:
+            border = plan.export()[3]
+        finally:
+            torch.cuda.current_stream(vs.device).synchronize()
+            plan.close()
+        owned = not isinstance(surface, Surface)
+        surf = Surface(surface) if owned else surface
+        try:
+            return _relax_project(vs, faces, border, surf, steps)
+        finally:
+            if owned:
+                torch.cuda.current_stream(vs.device).synchronize()
+                surf.close()
+
+
+def _edge_report(vs, faces, target: float) -> dict:
+    """Lengths of the unique edges (``meshprep.MeshTopology``): the counts against the target and min / mean / max."""
+    from .meshprep import MeshTopology
+    edges = MeshTopology(faces, vs.shape[0], vs.device, with_f2f=False).edges
+    if edges.shape[0] == 0:
+        return {"n_edges": 0, "n_short": 0, "edge_min": None, "edge_mean": None, "edge_max": None}
+    length = (vs[edges[:, 0]] - vs[edges[:, 1]]).norm(dim=1)
+    return {"n_edges": int(edges.shape[0]), "n_short": int((length < 0.8 * target).sum()),
+            "edge_min": float(length.min()), "edge_mean": float(prepare.mean_edge_length(vs, edges)), "edge_max": float(length.max())}
+
+
+def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.6, iterations: int = 5,
+                split_rounds: int = 64, flip_rounds: int = 32, relax_steps: int = 1, timings: bool = False) -> Refined:
+    """Refine ``mesh`` to the edge length ``target`` (default: ``target_percent`` % of the box diagonal) by ``iterations``
+    of split -> flip -> relax_project against the input's surface (module docstring, 4.).  ``timings``: also measure the
+    device time of the stages (``Refined.stage_ms``; one more synchronisation)."""
+    from .holes import _Stages
+    iterations = _check_rounds(iterations, "iterations")
+    split_rounds, flip_rounds = _check_rounds(split_rounds, "split_rounds"), _check_rounds(flip_rounds, "flip_rounds")
+    relax_steps = _check_rounds(relax_steps, "relax_steps")
+    if target is not None:
+        target = _check_target(target)
+    else:
+        target_percent = _check_target(target_percent, "target_percent")
+    _check_mesh(mesh)
+    vs, faces = _vs_faces(mesh)
+    V0 = vs.shape[0]
+    with capi._on_device(vs.device):
+        if target is None:
+            if V0 == 0:
+                raise ValueError("refine_mesh: an empty mesh has no box diagonal; give target")
+            diag = float((vs.max(0).values.double() - vs.min(0).values.double()).norm())
+            target = _check_target(target_percent / 100.0 * diag, "target (target_percent of the box diagonal)")
+        thr2 = split_threshold(target)
+        _plan(vs, faces).close()                                  # refuse an invalid input before anything is built
+        ms = {}
+
+        def add(stages):
+            for k, v in (stages.result() or {}).items():
+                ms[k] = ms.get(k, 0.0) + v
+
+        st = _Stages(vs.device, timings)
+        surf = Surface(vs, faces)
+        st.mark("surface")
+        add(st)
+        parents = torch.arange(V0, dtype=torch.int64, device=vs.device)[:, None].repeat(1, 2)
+        rounds, dev_start = [], None
+        try:
+            for _ in range(iterations):
+                st = _Stages(vs.device, timings)
+                plan = _plan(vs, faces)
+                try:
+                    if dev_start is None:
+                        dev_start = plan.flip(0)[1]
+                        st.mark("report")
+                    counts, n_long = plan.split(thr2, split_rounds)
+                    st.mark("split")
+                    flips, before, after = plan.flip(flip_rounds)
+                    vs, faces, par, border = plan.export()
+                    st.mark("flip")
+                finally:
+                    torch.cuda.current_stream(vs.device).synchronize()
+                    plan.close()
+                parents = torch.cat([parents, par[parents.shape[0]:]])
+                vs = _relax_project(vs, faces, border, surf, relax_steps)
+                st.mark("relax")
+                add(st)
+                rounds.append({"split": counts, "flip": flips, "n_long": n_long, "deviation_after_split": before,
+                               "deviation_after_flip": after})
+            # closing: relax_project can push an edge back over the threshold.  Split again (all rounds), project only what
+            # was inserted, and repeat until a pass finds nothing to split: then no position changed after the last analysis,
+            # so n_long == 0 in the report means that no edge of the RESULT has len2 > thr2, exactly.
+            st = _Stages(vs.device, timings)
+            closing, n_long, dev_end = [], None, None
+            for _ in range(CLOSING_PASSES + 1 if iterations > 0 else 1):
+                plan = _plan(vs, faces)
+                try:
+                    last = len(closing) == CLOSING_PASSES or iterations == 0
+                    counts, n_long = plan.split(thr2, 0 if last else split_rounds)
+                    if not counts:
+                        dev_end = plan.flip(0)[1]
+                        break
+                    n_before = vs.shape[0]
+                    vs, faces, par, border = plan.export()
+                finally:
+                    torch.cuda.current_stream(vs.device).synchronize()
+                    plan.close()
+                closing.append(sum(counts))
+                parents = torch.cat([parents, par[n_before:]])
+                closest = surf.query(vs[n_before:], signed=False)[2]
+                vs[n_before:] = torch.where(border[n_before:, None], vs[n_before:], closest)
+            st.mark("split")
+            dev_start = dev_end if dev_start is None else dev_start
+        finally:
+            torch.cuda.current_stream(vs.device).synchronize()
+            surf.close()
+        report = {"target": target, "iterations": rounds, "closing": closing, "n_long": n_long, "deviation_start": dev_start, "deviation_end": dev_end,
+                  "n_vertices": int(vs.shape[0]), "n_faces": int(faces.shape[0])}
+        report.update(_edge_report(vs, faces, target))
+        st.mark("report")
+        add(st)
+    return Refined(vs, faces, parents, report, ms if timings else None)
+
+
+def main(argv=None) -> int:
+    from . import synth
+    ap = argparse.ArgumentParser(prog="python -m semigcn_amd.remesh",
+                                 description="refine a triangle mesh to a target edge length: split, flip, relax and project "
+                                             "(the isotropic remesh of preprocess/prepare.py without edge collapse)")
+    ap.add_argument("input", nargs="?", help="the mesh to refine (OBJ)")
+    ap.add_argument("output", nargs="?", help="where the refined mesh goes (OBJ)")
+    ap.add_argument("--target", type=float, default=None, help="target edge length")
+    ap.add_argument("--target-percent", type=float, default=0.6, help="target as a percentage of the box diagonal")
+    ap.add_argument("--iterations", type=int, default=5)
+    ap.add_argument("--torus", type=int, nargs=2, metavar=("NU", "NV"), help="run on a synthetic torus instead of an OBJ")
+    ap.add_argument("--stretch", type=float, default=1.0, help="with --torus: scale x by this factor")
+    ap.add_argument("--repeat", type=int, default=1, help="run this many times and report the last (the first ones warm up)")
+    args = ap.parse_args(argv)
+    if (args.input is None) == (args.torus is None):
+        ap.error("give either in.obj out.obj or --torus NU NV")
+    if args.input is not None and args.output is None:
+        ap.error("in.obj needs out.obj")
+    if args.iterations < 0 or args.repeat < 1 or not args.stretch > 0:
+        ap.error("--iterations must be >= 0, --repeat >= 1 and --stretch > 0")
+    if args.input is not None:
+        mesh = read_obj(args.input)
+    else:
+        m = synth.torus_mesh(args.torus[0], args.torus[1], masks=False)
+        mesh = ((m.vs * np.array([args.stretch, 1.0, 1.0])).astype(np.float32), m.faces)
+    for _ in range(args.repeat):
+        out = refine_mesh(mesh, target=args.target, target_percent=args.target_percent, iterations=args.iterations, timings=True)
+    if args.output:
+        prepare.write_obj(args.output, out.vs, out.faces)
+    nv, nf = (int(x.shape[0]) for x in _vs_faces(mesh))
+    rep = dict(out.report)
+    its = rep.pop("iterations")
+    rep["n_closing"] = rep.pop("closing")
+    rec = {"n_vertices_in": nv, "n_faces_in": nf, "split_rounds": [len(i["split"]) for i in its],
+           "flip_rounds": [len(i["flip"]) for i in its], "n_split": [sum(i["split"]) for i in its],
+           "n_flipped": [sum(i["flip"]) for i in its]}
+    rec.update(rep)
+    rec.update({k: round(v, 4) for k, v in out.stage_ms.items()})
+    rec["total_ms"] = round(sum(out.stage_ms.values()), 4)
+    print(json.dumps(rec))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
