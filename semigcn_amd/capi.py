@@ -1293,9 +1293,34 @@ def face_mask_bits(faces: torch.Tensor, vbits: torch.Tensor) -> torch.Tensor:
     return out
 
 
-class SurfaceHandle:
+class _OwnedHandle:
+    """What the classes that own one mesh object of the library share: the handle ``_h``, the entry point that destroys
+    it, and closing it once -- by ``close()`` or when the object goes."""
+
+    _h = None
+    _destroy = ""          # name of the sg_*_destroy entry point
+
+    def _open(self):
+        if not self._h.value:
+            raise SemigcnLibraryError(f"{type(self).__name__} is closed")
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            getattr(load(), self._destroy)(self._h)
+            self._h = c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SurfaceHandle(_OwnedHandle):
     """Owns one sg_surface: the bounding-volume hierarchy over the triangles of one surface (the closest-point query of
     check/dist_check.py:13-67)."""
+
+    _destroy = "sg_surface_destroy"
 
     def __init__(self, vs: torch.Tensor, faces: torch.Tensor):
         _require_device(vs, "vs")
@@ -1367,17 +1392,6 @@ class SurfaceHandle:
                                                 _ptr(pairs), _stream(vs)), "sg_surface_self_pairs")
         return pairs
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            load().sg_surface_destroy(self._h)
-            self._h = c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def mesh_distance_reduce(q: torch.Tensor, gt_vs: torch.Tensor, q_org: Optional[torch.Tensor] = None, eps: float = 0.05,
                          hole: Optional[torch.Tensor] = None):
@@ -1427,10 +1441,12 @@ def mean_edge_length(vs: torch.Tensor, edges: torch.Tensor) -> torch.Tensor:
     return out
 
 
-class SmoothPlan:
+class SmoothPlan(_OwnedHandle):
     """Owns one sg_smooth: the weighted neighbour lists of uniform Laplacian smoothing with MeshLab's border rule
     (preprocess/prepare.py:110-114; the rule is stated in semigcn_amd/prepare.py::laplacian_smooth) and the two position
     buffers the steps ping-pong between.  One ``run`` at a time per plan."""
+
+    _destroy = "sg_smooth_destroy"
 
     def __init__(self, faces: torch.Tensor, num_vertices: int):
         _require_device(faces, "faces")
@@ -1455,8 +1471,7 @@ class SmoothPlan:
             raise SemigcnLibraryError(f"vs must be float32 [{self.num_vertices}, 3], got {vs.dtype} {tuple(vs.shape)}")
         if vs.device != self.device:
             raise SemigcnLibraryError(f"vs on {vs.device}, plan on {self.device}")
-        if not self._h.value:
-            raise SemigcnLibraryError("SmoothPlan is closed")
+        self._open()
         if movable is not None:
             _require_device(movable, "movable")
             if movable.numel() != self.num_vertices or movable.device != self.device:
@@ -1469,22 +1484,13 @@ class SmoothPlan:
             _check(load().sg_smooth_run(self._h, _ptr(vs), _ptr(out), _ptr(movable), steps, _stream(vs)), "sg_smooth_run")
         return out
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            load().sg_smooth_destroy(self._h)
-            self._h = c_void_p(0)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class FillPlan:
+class FillPlan(_OwnedHandle):
     """Owns one sg_fill (csrc/mesh_fill.hip): the boundary loops of a triangle list and, after ``plan``, the sizes of the
     patches that close them (the construction is specified in semigcn_amd/holes.py).  ``n_repeated`` / ``n_bowtie`` /
     ``bad_vertex`` say why a boundary cannot be ordered; ``loops`` / ``plan`` / ``emit`` then raise."""
+
+    _destroy = "sg_fill_destroy"
 
     def __init__(self, faces: torch.Tensor, num_vertices: int):
         _require_device(faces, "faces")
@@ -1510,10 +1516,6 @@ class FillPlan:
     @property
     def orderable(self) -> bool:
         return self.n_repeated == 0 and self.n_bowtie == 0
-
-    def _open(self):
-        if not self._h.value:
-            raise SemigcnLibraryError("FillPlan is closed")
 
     def loops(self):
         """(loop_ptr int64 [L + 1], loop_verts int64 [sum n]) on the plan's device."""
@@ -1557,22 +1559,13 @@ class FillPlan:
                    "sg_fill_emit")
         return filled[: self.num_loops]
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            load().sg_fill_destroy(self._h)
-            self._h = c_void_p(0)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PartsPlan:
+class PartsPlan(_OwnedHandle):
     """Owns one sg_parts (csrc/mesh_parts.hip): the connected components of a triangle list (the definitions are specified
     in semigcn_amd/components.py).  ``select`` marks what a ``keep`` over the components retains, ``emit`` writes the
     compacted mesh of the last ``select``; ``select`` may be called again with another ``keep``."""
+
+    _destroy = "sg_parts_destroy"
 
     CONNECTIVITY = {"edge": 0, "vertex": 1}
 
@@ -1599,10 +1592,6 @@ class PartsPlan:
         info = (c_int64 * 8)()
         _check(load().sg_parts_query(self._h, info), "sg_parts_query")
         return list(info)
-
-    def _open(self):
-        if not self._h.value:
-            raise SemigcnLibraryError("PartsPlan is closed")
 
     def labels(self):
         """(face_label int64 [F], -1 = degenerate; face_count int64 [K]) on the plan's device."""
@@ -1651,23 +1640,14 @@ class PartsPlan:
                                         none_if_empty(vertex_ids), none_if_empty(face_ids), _stream(vs)), "sg_parts_emit")
         return new_vs, new_faces, vertex_ids, face_ids
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            load().sg_parts_destroy(self._h)
-            self._h = c_void_p(0)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class RemeshPlan:
+class RemeshPlan(_OwnedHandle):
     """Owns one sg_remesh (csrc/mesh_remesh.hip): a copy of a mesh on the device that ``split`` and ``flip`` refine in place
     (the rules are specified in semigcn_amd/remesh.py) and ``export`` hands back.  ``n_nonmanifold`` / ``n_misoriented`` /
     ``n_degenerate`` / ``n_nonfinite`` with ``bad_edge`` / ``bad_face`` / ``bad_vertex`` say why an input is refused;
     ``split`` and ``flip`` then raise."""
+
+    _destroy = "sg_remesh_destroy"
 
     def __init__(self, vs: torch.Tensor, faces: torch.Tensor):
         _require_device(vs, "vs")
@@ -1697,10 +1677,6 @@ class RemeshPlan:
         info = (c_int64 * 16)()
         _check(load().sg_remesh_query(self._h, info), "sg_remesh_query")
         return list(info)
-
-    def _open(self):
-        if not self._h.value:
-            raise SemigcnLibraryError("RemeshPlan is closed")
 
     def _sizes(self):
         self.num_vertices, self.num_faces = (int(v) for v in self._query()[:2])
@@ -1744,17 +1720,6 @@ class RemeshPlan:
             _check(load().sg_remesh_export(self._h, none_if_empty(vs), none_if_empty(faces), none_if_empty(parents),
                                            none_if_empty(border), _stream(vs)), "sg_remesh_export")
         return vs, faces, parents, border
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            load().sg_remesh_destroy(self._h)
-            self._h = c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _raw_stream_of(device: torch.device) -> int:

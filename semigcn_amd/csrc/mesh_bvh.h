@@ -1,13 +1,13 @@
 // The surface hierarchy as its traversals see it: what mesh_dist.hip (build, closest-point query) and mesh_isect.hip
 // (self-overlap query) both need to know about an sg_surface and the layout of its nodes.  Nothing else is shared.
 #pragma once
-#include "sg_common.h"
+#include "mesh_common.h"
 
 struct sg_surface {
   int64_t V = 0, F = 0, L = 0;   // vertices, faces, leaves
-  float4* tri = nullptr;         // [3F] in leaf order: (a, face id bits), (b - a, 0), (c - a, 0)
-  float4* nodes = nullptr;       // [max(L - 1, 1)][4]: child 0 lo (w: child code), hi, child 1 lo (w: code), hi
-  float* bounds = nullptr;       // [6] box of the face centroids (the query points' Morton frame)
+  sg::DeviceBuf<float4> tri;     // [3F] in leaf order: (a, face id bits), (b - a, 0), (c - a, 0)
+  sg::DeviceBuf<float4> nodes;   // [max(L - 1, 1)][4]: child 0 lo (w: child code), hi, child 1 lo (w: code), hi
+  sg::DeviceBuf<float> bounds;   // [6] box of the face centroids (the query points' Morton frame)
 };
 
 namespace sg {

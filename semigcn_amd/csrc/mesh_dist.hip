@@ -15,18 +15,16 @@
 //
 // Point-triangle arithmetic runs in the triangle's local frame (p - a, b - a, c - a): the rounding
 // error then scales with the distance and the triangle size, not with the coordinates.
-#include <hipcub/hipcub.hpp>
+#include <memory>
+#include <new>
 
-#include "mesh_bvh.h"   // struct sg_surface, kLeaf, kStack, the child codes
+#include "mesh_bvh.h"   // struct sg_surface, kLeaf, kStack, the child codes; mesh_common.h
 
 namespace sg {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kQueryThreads = 64; // one wavefront per workgroup: its stack is 64 x 64 int32 = 16 KiB of LDS
 constexpr int kRedBlocks = 1024;  // fixed grid of the metric reduction: a fixed summation order
-
-inline int blocks_for(int64_t n) { return (int)((n + kThreads - 1) / kThreads); }
 
 __device__ __forceinline__ uint64_t spread3(uint64_t x) {   // 21 bits -> every third bit of 63
   x &= 0x1fffffull;
@@ -408,92 +406,67 @@ __global__ void metric_finish(const double* __restrict__ part, int nb, double* _
   out[3] = sqrt(dx * dx + dy * dy + dz * dz);
 }
 
-// Stream-ordered temporaries: no host synchronisation to free them.
-struct AsyncBuf {
-  void* p = nullptr;
-  hipStream_t s = nullptr;
-  explicit AsyncBuf(hipStream_t st) : s(st) {}
-  hipError_t alloc(size_t bytes) { return hipMallocAsync(&p, bytes ? bytes : 16, s); }
-  ~AsyncBuf() { if (p) (void)hipFreeAsync(p, s); }
-};
-
-int bits_for(uint64_t n) {
-  int b = 1;
-  while (b < 63 && (n >> b) != 0) ++b;
-  return b;
-}
-
 }  // namespace
 
-void destroy_surface(sg_surface* s) {
-  if (!s) return;
-  if (s->tri) (void)hipFree(s->tri);
-  if (s->nodes) (void)hipFree(s->nodes);
-  if (s->bounds) (void)hipFree(s->bounds);
-  delete s;
-}
+void destroy_surface(sg_surface* s) { delete s; }
 
 int surface_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, hipStream_t stream, sg_surface** out) {
   SG_REQUIRE(F < ((int64_t)1 << 31) - kLeaf && V < ((int64_t)1 << 31), "sg_surface_create: sizes must fit int32");
   {   // the face-index check comes first: nothing below reads a vertex through an index before it has passed
-    AsyncBuf bad(stream);
-    SG_HIP_TRY(bad.alloc(sizeof(int)));
+    AsyncBuf<int> bad(stream);
+    SG_HIP_TRY(bad.alloc(1));
     SG_HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(int), stream));
-    check_faces<<<blocks_for(3 * F), kThreads, 0, stream>>>(faces, 3 * F, V, (int*)bad.p);
+    check_faces<<<blocks_for(3 * F), kThreads, 0, stream>>>(faces, 3 * F, V, bad.p);
     SG_HIP_TRY(hipGetLastError());
     int h_bad = 0;
     SG_HIP_TRY(hipMemcpyAsync(&h_bad, bad.p, sizeof(int), hipMemcpyDeviceToHost, stream));
     SG_HIP_TRY(hipStreamSynchronize(stream));
     SG_REQUIRE(!h_bad, "sg_surface_create: face refers to a vertex outside [0, %lld)", (long long)V);
   }
-  sg_surface* s = new (std::nothrow) sg_surface;
+  std::unique_ptr<sg_surface> s(new (std::nothrow) sg_surface);
   SG_REQUIRE(s != nullptr, "sg_surface_create: out of host memory");
-  struct Guard {
-    sg_surface* s;
-    ~Guard() { destroy_surface(s); }
-  } guard{s};
   const int64_t L = (F + kLeaf - 1) / kLeaf, n_nodes = L > 1 ? L - 1 : 1;
   s->V = V;
   s->F = F;
   s->L = L;
-  SG_HIP_TRY(hipMalloc(&s->tri, (size_t)F * 3 * sizeof(float4)));
-  SG_HIP_TRY(hipMalloc(&s->nodes, (size_t)n_nodes * 4 * sizeof(float4)));
-  SG_HIP_TRY(hipMalloc(&s->bounds, 6 * sizeof(float)));
+  SG_HIP_TRY(s->tri.alloc(3 * F));
+  SG_HIP_TRY(s->nodes.alloc(4 * n_nodes));
+  SG_HIP_TRY(s->bounds.alloc(6));
 
   const int nb = blocks_for(F) < kRedBlocks ? blocks_for(F) : kRedBlocks;
-  AsyncBuf part(stream), keys_a(stream), keys_b(stream), temp(stream), pleaf(stream), pnode(stream), arrivals(stream);
-  SG_HIP_TRY(part.alloc((size_t)nb * 6 * sizeof(float)));
-  bounds_partial<<<nb, kThreads, 0, stream>>>(vs, faces, F, (float*)part.p);
-  bounds_finish<<<1, 64, 0, stream>>>((const float*)part.p, nb, s->bounds);
+  AsyncBuf<float> part(stream);
+  AsyncBuf<uint64_t> keys_a(stream), keys_b(stream);
+  AsyncBuf<char> temp(stream);
+  AsyncBuf<int64_t> pleaf(stream), pnode(stream);
+  AsyncBuf<int> arrivals(stream);
+  SG_HIP_TRY(part.alloc((size_t)nb * 6));
+  bounds_partial<<<nb, kThreads, 0, stream>>>(vs, faces, F, part.p);
+  bounds_finish<<<1, 64, 0, stream>>>(part.p, nb, s->bounds.p);
   SG_HIP_TRY(hipGetLastError());
 
-  const int idx_bits = bits_for((uint64_t)F);
+  const int idx_bits = bits_for((uint64_t)F, 63);
   int mbits = (64 - idx_bits) / 3;
   if (mbits > 21) mbits = 21;
-  SG_HIP_TRY(keys_a.alloc((size_t)F * sizeof(uint64_t)));
-  SG_HIP_TRY(keys_b.alloc((size_t)F * sizeof(uint64_t)));
-  face_keys<<<blocks_for(F), kThreads, 0, stream>>>(vs, faces, F, s->bounds, mbits, idx_bits, (uint64_t*)keys_a.p);
+  SG_HIP_TRY(keys_a.alloc(F));
+  SG_HIP_TRY(keys_b.alloc(F));
+  face_keys<<<blocks_for(F), kThreads, 0, stream>>>(vs, faces, F, s->bounds.p, mbits, idx_bits, keys_a.p);
   SG_HIP_TRY(hipGetLastError());
   size_t tb = 0;
-  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p, (int)F, 0,
-                                               3 * mbits + idx_bits, stream));
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, keys_a.p, keys_b.p, (int)F, 0, 3 * mbits + idx_bits, stream));
   SG_HIP_TRY(temp.alloc(tb));
-  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp.p, tb, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p, (int)F, 0,
-                                               3 * mbits + idx_bits, stream));
-  const uint64_t* keys = (const uint64_t*)keys_b.p;
-  gather_tris<<<blocks_for(F), kThreads, 0, stream>>>(vs, faces, F, keys, ((uint64_t)1 << idx_bits) - 1, s->tri);
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp.p, tb, keys_a.p, keys_b.p, (int)F, 0, 3 * mbits + idx_bits, stream));
+  const uint64_t* keys = keys_b.p;
+  gather_tris<<<blocks_for(F), kThreads, 0, stream>>>(vs, faces, F, keys, ((uint64_t)1 << idx_bits) - 1, s->tri.p);
   SG_HIP_TRY(hipGetLastError());
 
-  SG_HIP_TRY(pleaf.alloc((size_t)L * sizeof(int64_t)));
-  SG_HIP_TRY(pnode.alloc((size_t)n_nodes * sizeof(int64_t)));
-  SG_HIP_TRY(arrivals.alloc((size_t)n_nodes * sizeof(int)));
+  SG_HIP_TRY(pleaf.alloc(L));
+  SG_HIP_TRY(pnode.alloc(n_nodes));
+  SG_HIP_TRY(arrivals.alloc(n_nodes));
   SG_HIP_TRY(hipMemsetAsync(arrivals.p, 0, (size_t)n_nodes * sizeof(int), stream));
-  karras_nodes<<<blocks_for(n_nodes), kThreads, 0, stream>>>(keys, L, s->nodes, (int64_t*)pleaf.p, (int64_t*)pnode.p);
-  refit<<<blocks_for(L), kThreads, 0, stream>>>(vs, faces, s->tri, F, L, (const int64_t*)pleaf.p,
-                                                (const int64_t*)pnode.p, s->nodes, (int*)arrivals.p);
+  karras_nodes<<<blocks_for(n_nodes), kThreads, 0, stream>>>(keys, L, s->nodes.p, pleaf.p, pnode.p);
+  refit<<<blocks_for(L), kThreads, 0, stream>>>(vs, faces, s->tri.p, F, L, pleaf.p, pnode.p, s->nodes.p, arrivals.p);
   SG_HIP_TRY(hipGetLastError());
-  guard.s = nullptr;
-  *out = s;
+  *out = s.release();
   return SG_OK;
 }
 
@@ -501,20 +474,19 @@ int surface_query(const sg_surface* s, const float* pts, int64_t N, int signed_d
                   float* closest, hipStream_t stream) {
   SG_REQUIRE(N < ((int64_t)1 << 31), "sg_surface_query: N must fit int32");
   if (N == 0) return SG_OK;
-  AsyncBuf keys_a(stream), keys_b(stream), temp(stream);
-  SG_HIP_TRY(keys_a.alloc((size_t)N * sizeof(uint64_t)));
-  SG_HIP_TRY(keys_b.alloc((size_t)N * sizeof(uint64_t)));
-  point_keys<<<blocks_for(N), kThreads, 0, stream>>>(pts, N, s->bounds, (uint64_t*)keys_a.p);
+  AsyncBuf<uint64_t> keys_a(stream), keys_b(stream);
+  AsyncBuf<char> temp(stream);
+  SG_HIP_TRY(keys_a.alloc(N));
+  SG_HIP_TRY(keys_b.alloc(N));
+  point_keys<<<blocks_for(N), kThreads, 0, stream>>>(pts, N, s->bounds.p, keys_a.p);
   SG_HIP_TRY(hipGetLastError());
   size_t tb = 0;
-  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p, (int)N, 0, 62,
-                                               stream));
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, keys_a.p, keys_b.p, (int)N, 0, 62, stream));
   SG_HIP_TRY(temp.alloc(tb));
-  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp.p, tb, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p, (int)N, 0, 62,
-                                               stream));
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp.p, tb, keys_a.p, keys_b.p, (int)N, 0, 62, stream));
   const int64_t nb = (N + kQueryThreads - 1) / kQueryThreads;
-  surface_query<<<(unsigned)nb, kQueryThreads, 0, stream>>>(s->nodes, s->tri, s->F, (const uint64_t*)keys_b.p, N, pts,
-                                                            signed_dist, dist, face, closest);
+  surface_query<<<(unsigned)nb, kQueryThreads, 0, stream>>>(s->nodes.p, s->tri.p, s->F, keys_b.p, N, pts, signed_dist, dist,
+                                                            face, closest);
   SG_HIP_TRY(hipGetLastError());
   return SG_OK;
 }
@@ -522,10 +494,10 @@ int surface_query(const sg_surface* s, const float* pts, int64_t N, int signed_d
 int mesh_distance_reduce(const float* q, const float* q_org, float eps, const uint8_t* hole_in, const float* gt_vs,
                          int64_t N, uint8_t* hole_out, double* out, hipStream_t stream) {
   const int nb = N == 0 ? 1 : (blocks_for(N) < kRedBlocks ? blocks_for(N) : kRedBlocks);
-  AsyncBuf part(stream);
-  SG_HIP_TRY(part.alloc((size_t)nb * 9 * sizeof(double)));
-  metric_partial<<<nb, kThreads, 0, stream>>>(q, q_org, eps, hole_in, gt_vs, N, hole_out, (double*)part.p);
-  metric_finish<<<1, 64, 0, stream>>>((const double*)part.p, nb, out);
+  AsyncBuf<double> part(stream);
+  SG_HIP_TRY(part.alloc((size_t)nb * 9));
+  metric_partial<<<nb, kThreads, 0, stream>>>(q, q_org, eps, hole_in, gt_vs, N, hole_out, part.p);
+  metric_finish<<<1, 64, 0, stream>>>(part.p, nb, out);
   SG_HIP_TRY(hipGetLastError());
   return SG_OK;
 }

@@ -15,41 +15,30 @@
 //   faces     one thread per new face: strips between rings advance by floor((t + 1) m / (m + k)) > floor(t m / (m + k)).
 //
 // All of it is integer work and gathers bound by HBM traffic; the only sort of full size is the one over the half-edges.
-#include <hipcub/hipcub.hpp>
-
-#include <initializer_list>
+#include <memory>
 #include <new>
 
-#include "sg_common.h"
+#include "mesh_common.h"
 
 struct sg_fill {
   int64_t V = 0, F = 0, nb = 0, L = 0;
   int64_t n_dup = 0, n_bow = 0, bad_vertex = -1;
-  int64_t* loop_ptr = nullptr;     // [L + 1]
-  int64_t* loop_verts = nullptr;   // [nb]
+  sg::DeviceBuf<int64_t> loop_ptr;     // [L + 1]
+  sg::DeviceBuf<int64_t> loop_verts;   // [nb]
   // sizes of the patches (fill_plan)
   bool planned = false;
   int64_t Vn = 0, Fn = 0, NR = 0;
-  uint8_t* filled = nullptr;       // [L]
-  int64_t* counts = nullptr;       // [3][L + 1]: new vertices, new faces, ring-table entries of every loop
-  int64_t* base = nullptr;         // [3][L + 1]: their exclusive scans
-  int64_t* ring_v = nullptr;       // [NR] per loop R + 1 entries: new vertices in rings 1 .. r
-  int64_t* ring_f = nullptr;       // [NR] per loop R + 1 entries: new faces in strips 0 .. r - 1
-  double* cum = nullptr;           // [nb] arc length from the loop's first vertex to vertex i
-  double* geo = nullptr;           // [L][4] perimeter, centre x y z
+  sg::DeviceBuf<uint8_t> filled;       // [L]
+  sg::DeviceBuf<int64_t> counts;       // [3][L + 1]: new vertices, new faces, ring-table entries of every loop
+  sg::DeviceBuf<int64_t> base;         // [3][L + 1]: their exclusive scans
+  sg::DeviceBuf<int64_t> ring_v;       // [NR] per loop R + 1 entries: new vertices in rings 1 .. r
+  sg::DeviceBuf<int64_t> ring_f;       // [NR] per loop R + 1 entries: new faces in strips 0 .. r - 1
+  sg::DeviceBuf<double> cum;           // [nb] arc length from the loop's first vertex to vertex i
+  sg::DeviceBuf<double> geo;           // [L][4] perimeter, centre x y z
 };
 
 namespace sg {
 namespace {
-
-constexpr int kThreads = 256;
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-struct DeviceBuf {
-  void* p = nullptr;
-  ~DeviceBuf() { if (p) (void)hipFree(p); }
-};
 
 // ---- the construction's integers -------------------------------------------------------------------------------------
 __device__ inline int64_t ring_count(int64_t n) {
@@ -85,7 +74,7 @@ __global__ void fill_keys(const int64_t* __restrict__ faces, int64_t n_half, int
   if (h >= n_half) return;
   const int64_t f = h / 3;
   const int i = (int)(h - 3 * f);
-  const int64_t a = faces[3 * f + i], b = faces[3 * f + (i == 2 ? 0 : i + 1)];
+  const int64_t a = faces[3 * f + i], b = faces[3 * f + next3(i)];
   uint64_t key = ~0ull;
   if (a < 0 || a >= V || b < 0 || b >= V) {
     flags[0] = 1;
@@ -393,212 +382,32 @@ __global__ __launch_bounds__(kThreads) void emit_faces(const int64_t* __restrict
   out[3 * g + 2] = f2;
 }
 
-int exclusive_sum(const int64_t* in, int64_t* out, int64_t n, hipStream_t stream) {
-  size_t tb = 0;
-  SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, stream));
-  DeviceBuf temp;
-  SG_HIP_TRY(hipMalloc(&temp.p, tb ? tb : 16));
-  SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(temp.p, tb, in, out, (int)n, stream));
-  SG_HIP_TRY(hipStreamSynchronize(stream));     // the temporary is freed on return
-  return SG_OK;
-}
-
 void free_sizes(sg_fill* s) {
-  for (void* p : {(void*)s->filled, (void*)s->counts, (void*)s->base, (void*)s->ring_v, (void*)s->ring_f, (void*)s->cum,
-                  (void*)s->geo})
-    if (p) (void)hipFree(p);
-  s->filled = nullptr;
-  s->counts = s->base = s->ring_v = s->ring_f = nullptr;
-  s->cum = s->geo = nullptr;
+  s->filled.reset();
+  s->counts.reset();
+  s->base.reset();
+  s->ring_v.reset();
+  s->ring_f.reset();
+  s->cum.reset();
+  s->geo.reset();
   s->planned = false;
   s->Vn = s->Fn = s->NR = 0;
 }
 
-}  // namespace
-
-void destroy_fill(sg_fill* s) {
-  if (!s) return;
-  free_sizes(s);
-  if (s->loop_ptr) (void)hipFree(s->loop_ptr);
-  if (s->loop_verts) (void)hipFree(s->loop_verts);
-  delete s;
-}
-
-int fill_create(const int64_t* faces, int64_t F, int64_t V, hipStream_t stream, sg_fill** out) {
-  const int64_t n_half = 3 * F;
-  SG_REQUIRE(V < ((int64_t)1 << 31) && n_half < ((int64_t)1 << 31), "sg_fill_create: sizes must fit int32");
-  sg_fill* s = new (std::nothrow) sg_fill;
-  SG_REQUIRE(s != nullptr, "sg_fill_create: out of host memory");
-  struct Guard {
-    sg_fill* s;
-    ~Guard() { destroy_fill(s); }
-  } guard{s};
-  s->V = V;
-  s->F = F;
-  SG_HIP_TRY(hipMalloc(&s->loop_ptr, sizeof(int64_t)));
-  SG_HIP_TRY(hipMemsetAsync(s->loop_ptr, 0, sizeof(int64_t), stream));
-  if (F == 0) {
-    SG_HIP_TRY(hipStreamSynchronize(stream));
-    guard.s = nullptr;
-    *out = s;
-    return SG_OK;
-  }
-
-  DeviceBuf keys_a, keys_b, marks, picked, count, flags, stats, temp;
-  int h_flags[2] = {0, 0}, h_count = 0;
-  unsigned long long h_stats[4] = {0, 0, ~0ull, 0};
-  SG_HIP_TRY(hipMalloc(&keys_a.p, (size_t)n_half * sizeof(uint64_t)));
-  SG_HIP_TRY(hipMalloc(&keys_b.p, (size_t)n_half * sizeof(uint64_t)));
-  SG_HIP_TRY(hipMalloc(&marks.p, (size_t)n_half));
-  SG_HIP_TRY(hipMalloc(&picked.p, (size_t)n_half * sizeof(uint64_t)));
-  SG_HIP_TRY(hipMalloc(&count.p, sizeof(int)));
-  SG_HIP_TRY(hipMalloc(&flags.p, sizeof(h_flags)));
-  SG_HIP_TRY(hipMalloc(&stats.p, sizeof(h_stats)));
-  SG_HIP_TRY(hipMemsetAsync(flags.p, 0, sizeof(h_flags), stream));
-  SG_HIP_TRY(hipMemcpyAsync(stats.p, h_stats, sizeof(h_stats), hipMemcpyHostToDevice, stream));
-  fill_keys<<<blocks_for(n_half), kThreads, 0, stream>>>(faces, n_half, V, (uint64_t*)keys_a.p, (int*)flags.p);
-  SG_HIP_TRY(hipGetLastError());
-  int hi_bits = 1;
-  while (hi_bits < 31 && ((uint64_t)V >> hi_bits) != 0) ++hi_bits;
-  size_t t1 = 0, t2 = 0;
-  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p, (int)n_half, 0,
-                                               33 + hi_bits, stream));
-  SG_HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, t2, (const uint64_t*)keys_b.p, (const uint8_t*)marks.p, (uint64_t*)picked.p,
-                                           (int*)count.p, (int)n_half, stream));
-  const size_t tb = t1 > t2 ? t1 : t2;
-  SG_HIP_TRY(hipMalloc(&temp.p, tb ? tb : 16));
-  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp.p, t1, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p, (int)n_half, 0,
-                                               33 + hi_bits, stream));
-  mark_boundary<<<blocks_for(n_half), kThreads, 0, stream>>>((const uint64_t*)keys_b.p, n_half, (uint8_t*)marks.p,
-                                                            (unsigned long long*)stats.p);
-  SG_HIP_TRY(hipGetLastError());
-  SG_HIP_TRY(hipcub::DeviceSelect::Flagged(temp.p, t2, (const uint64_t*)keys_b.p, (const uint8_t*)marks.p, (uint64_t*)picked.p,
-                                           (int*)count.p, (int)n_half, stream));
-  SG_HIP_TRY(hipMemcpyAsync(&h_count, count.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-  SG_HIP_TRY(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, stream));
-  SG_HIP_TRY(hipStreamSynchronize(stream));
-  SG_REQUIRE(!h_flags[0], "sg_fill_create: face refers to a vertex outside [0, %lld)", (long long)V);
-  SG_REQUIRE(!h_flags[1], "sg_fill_create: degenerate face (repeated vertex)");
-  SG_REQUIRE(h_count >= 0 && h_count <= n_half, "sg_fill_create: boundary count %d out of range", h_count);
-  const int64_t nb = h_count;
-
-  // the boundary half-edges as a << 32 | b, ascending: the sources are then the boundary vertices in ascending order
-  DeviceBuf bk, next;
-  uint64_t* d_bk = nullptr;
-  if (nb > 0) {
-    SG_HIP_TRY(hipMalloc(&bk.p, (size_t)nb * sizeof(uint64_t)));
-    SG_HIP_TRY(hipMalloc(&next.p, (size_t)nb * sizeof(int32_t)));
-    d_bk = (uint64_t*)bk.p;
-    uint64_t* unsorted = (uint64_t*)keys_a.p;           // the full-size buffers are free again
-    directed_from_keys<<<blocks_for(nb), kThreads, 0, stream>>>((const uint64_t*)picked.p, nb, unsorted);
-    SG_HIP_TRY(hipGetLastError());
-    size_t t3 = 0;
-    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, t3, (const uint64_t*)unsorted, d_bk, (int)nb, 0, 64, stream));
-    DeviceBuf temp3;
-    SG_HIP_TRY(hipMalloc(&temp3.p, t3 ? t3 : 16));
-    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp3.p, t3, (const uint64_t*)unsorted, d_bk, (int)nb, 0, 64, stream));
-    SG_HIP_TRY(hipMemsetAsync(next.p, 0xff, (size_t)nb * sizeof(int32_t), stream));
-    link_boundary<<<blocks_for(nb), kThreads, 0, stream>>>(d_bk, nb, (int32_t*)next.p, (unsigned long long*)stats.p);
-    check_links<<<blocks_for(nb), kThreads, 0, stream>>>((const int32_t*)next.p, nb, (unsigned long long*)stats.p);
-    SG_HIP_TRY(hipGetLastError());
-    SG_HIP_TRY(hipStreamSynchronize(stream));           // temp3 is freed here
-  }
-  SG_HIP_TRY(hipMemcpyAsync(h_stats, stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, stream));
-  SG_HIP_TRY(hipStreamSynchronize(stream));
-  s->n_dup = (int64_t)h_stats[0];
-  s->n_bow = (int64_t)h_stats[1];
-  if (s->n_dup || s->n_bow) {                           // unorderable: reported by sg_fill_query, nothing is walked
-    s->bad_vertex = (int64_t)h_stats[2];
-    guard.s = nullptr;
-    *out = s;
-    return SG_OK;
-  }
-  SG_REQUIRE(h_stats[3] == 0, "sg_fill_create: the boundary half-edges do not form a permutation (%llu broken links)",
-             h_stats[3]);
-  if (nb == 0) {
-    guard.s = nullptr;
-    *out = s;
-    return SG_OK;
-  }
-
-  // pointer jumping: after `rounds` rounds the window of every vertex is at least as long as the longest loop can be
-  DeviceBuf st_a, st_b, jp_a, jp_b, heads, loop_of, sizes;
-  SG_HIP_TRY(hipMalloc(&st_a.p, (size_t)nb * sizeof(uint64_t)));
-  SG_HIP_TRY(hipMalloc(&st_b.p, (size_t)nb * sizeof(uint64_t)));
-  SG_HIP_TRY(hipMalloc(&jp_a.p, (size_t)nb * sizeof(int32_t)));
-  SG_HIP_TRY(hipMalloc(&jp_b.p, (size_t)nb * sizeof(int32_t)));
-  SG_HIP_TRY(hipMalloc(&heads.p, (size_t)(nb + 1) * sizeof(int64_t)));
-  SG_HIP_TRY(hipMalloc(&loop_of.p, (size_t)(nb + 1) * sizeof(int64_t)));
-  uint64_t* st = (uint64_t*)st_a.p;
-  uint64_t* st_o = (uint64_t*)st_b.p;
-  int32_t* jp = (int32_t*)jp_a.p;
-  int32_t* jp_o = (int32_t*)jp_b.p;
-  jump_init<<<blocks_for(nb), kThreads, 0, stream>>>((const int32_t*)next.p, nb, st, jp);
-  for (uint64_t span = 1; span < (uint64_t)nb; span <<= 1) {
-    jump_round<<<blocks_for(nb), kThreads, 0, stream>>>(st, jp, nb, span, st_o, jp_o);
-    uint64_t* ts = st; st = st_o; st_o = ts;
-    int32_t* tj = jp; jp = jp_o; jp_o = tj;
-  }
-  SG_HIP_TRY(hipGetLastError());
-  SG_HIP_TRY(hipMemsetAsync((int64_t*)heads.p + nb, 0, sizeof(int64_t), stream));
-  loop_heads<<<blocks_for(nb), kThreads, 0, stream>>>(st, nb, (int64_t*)heads.p);
-  SG_HIP_TRY(hipGetLastError());
-  if (int rc = exclusive_sum((const int64_t*)heads.p, (int64_t*)loop_of.p, nb + 1, stream)) return rc;
-  int64_t L = 0;
-  SG_HIP_TRY(hipMemcpyAsync(&L, (int64_t*)loop_of.p + nb, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-  SG_HIP_TRY(hipStreamSynchronize(stream));
-  SG_REQUIRE(L >= 1 && L <= nb, "sg_fill_create: loop count %lld out of range", (long long)L);
-
-  SG_HIP_TRY(hipMalloc(&sizes.p, (size_t)(L + 1) * sizeof(int64_t)));
-  SG_HIP_TRY(hipMemsetAsync(sizes.p, 0, (size_t)(L + 1) * sizeof(int64_t), stream));
-  loop_sizes<<<blocks_for(nb), kThreads, 0, stream>>>(st, (const int32_t*)next.p, (const int64_t*)loop_of.p, nb, L,
-                                                     (int64_t*)sizes.p);
-  SG_HIP_TRY(hipGetLastError());
-  (void)hipFree(s->loop_ptr);
-  s->loop_ptr = nullptr;
-  SG_HIP_TRY(hipMalloc(&s->loop_ptr, (size_t)(L + 1) * sizeof(int64_t)));
-  SG_HIP_TRY(hipMalloc(&s->loop_verts, (size_t)nb * sizeof(int64_t)));
-  if (int rc = exclusive_sum((const int64_t*)sizes.p, s->loop_ptr, L + 1, stream)) return rc;
-  int64_t total = 0;
-  SG_HIP_TRY(hipMemcpyAsync(&total, s->loop_ptr + L, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-  SG_HIP_TRY(hipStreamSynchronize(stream));
-  SG_REQUIRE(total == nb, "sg_fill_create: the loops hold %lld vertices, the boundary %lld", (long long)total, (long long)nb);
-  SG_HIP_TRY(hipMemsetAsync(s->loop_verts, 0xff, (size_t)nb * sizeof(int64_t), stream));
-  loop_scatter<<<blocks_for(nb), kThreads, 0, stream>>>(st, (const int32_t*)next.p, (const int64_t*)loop_of.p, d_bk, s->loop_ptr,
-                                                       nb, L, s->loop_verts);
-  SG_HIP_TRY(hipGetLastError());
-  SG_HIP_TRY(hipStreamSynchronize(stream));             // the temporaries are freed on return
-  s->nb = nb;
-  s->L = L;
-  guard.s = nullptr;
-  *out = s;
-  return SG_OK;
-}
-
-int fill_plan(sg_fill* s, int64_t max_hole_edges, hipStream_t stream, int64_t* n_new_vertices, int64_t* n_new_faces) {
-  SG_REQUIRE(!s->n_dup && !s->n_bow, "sg_fill_plan: the boundary is unorderable (see sg_fill_query)");
-  free_sizes(s);
-  *n_new_vertices = *n_new_faces = 0;
+// the sizes of fill_plan for L > 0 loops; on an error the caller drops what was allocated
+int size_patches(sg_fill* s, int64_t max_hole_edges, hipStream_t stream) {
   const int64_t L = s->L, W = L + 1;
-  if (L == 0) {
-    s->planned = true;
-    return SG_OK;
-  }
-  struct Guard {
-    sg_fill* s;
-    ~Guard() { if (s) free_sizes(s); }
-  } guard{s};
-  SG_HIP_TRY(hipMalloc(&s->filled, (size_t)L));
-  SG_HIP_TRY(hipMalloc(&s->counts, (size_t)(3 * W) * sizeof(int64_t)));
-  SG_HIP_TRY(hipMalloc(&s->base, (size_t)(3 * W) * sizeof(int64_t)));
-  SG_HIP_TRY(hipMalloc(&s->cum, (size_t)s->nb * sizeof(double)));
-  SG_HIP_TRY(hipMalloc(&s->geo, (size_t)(4 * L) * sizeof(double)));
-  patch_counts<<<blocks_for(W), kThreads, 0, stream>>>(s->loop_ptr, L, max_hole_edges, s->filled, s->counts);
+  SG_HIP_TRY(s->filled.alloc(L));
+  SG_HIP_TRY(s->counts.alloc(3 * W));
+  SG_HIP_TRY(s->base.alloc(3 * W));
+  SG_HIP_TRY(s->cum.alloc(s->nb));
+  SG_HIP_TRY(s->geo.alloc(4 * L));
+  patch_counts<<<blocks_for(W), kThreads, 0, stream>>>(s->loop_ptr.p, L, max_hole_edges, s->filled.p, s->counts.p);
   SG_HIP_TRY(hipGetLastError());
   int64_t totals[3] = {0, 0, 0};
   for (int q = 0; q < 3; ++q) {
-    if (int rc = exclusive_sum(s->counts + q * W, s->base + q * W, W, stream)) return rc;
-    SG_HIP_TRY(hipMemcpyAsync(&totals[q], s->base + q * W + L, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    if (int rc = exclusive_sum(s->counts.p + q * W, s->base.p + q * W, W, stream)) return rc;
+    SG_HIP_TRY(hipMemcpyAsync(&totals[q], s->base.p + q * W + L, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
   }
   SG_HIP_TRY(hipStreamSynchronize(stream));
   SG_REQUIRE(totals[0] >= 0 && totals[1] >= 0 && totals[2] >= 0, "sg_fill_plan: negative totals");
@@ -608,13 +417,170 @@ int fill_plan(sg_fill* s, int64_t max_hole_edges, hipStream_t stream, int64_t* n
   s->Fn = totals[1];
   s->NR = totals[2];
   if (s->NR > 0) {
-    SG_HIP_TRY(hipMalloc(&s->ring_v, (size_t)s->NR * sizeof(int64_t)));
-    SG_HIP_TRY(hipMalloc(&s->ring_f, (size_t)s->NR * sizeof(int64_t)));
-    ring_tables<<<blocks_for(L), kThreads, 0, stream>>>(s->loop_ptr, L, s->filled, s->base + 2 * W, s->NR, s->ring_v, s->ring_f);
+    SG_HIP_TRY(s->ring_v.alloc(s->NR));
+    SG_HIP_TRY(s->ring_f.alloc(s->NR));
+    ring_tables<<<blocks_for(L), kThreads, 0, stream>>>(s->loop_ptr.p, L, s->filled.p, s->base.p + 2 * W, s->NR, s->ring_v.p,
+                                                       s->ring_f.p);
     SG_HIP_TRY(hipGetLastError());
   }
+  return SG_OK;
+}
+
+}  // namespace
+
+void destroy_fill(sg_fill* s) { delete s; }
+
+int fill_create(const int64_t* faces, int64_t F, int64_t V, hipStream_t stream, sg_fill** out) {
+  const int64_t n_half = 3 * F;
+  SG_REQUIRE(V < ((int64_t)1 << 31) && n_half < ((int64_t)1 << 31), "sg_fill_create: sizes must fit int32");
+  std::unique_ptr<sg_fill> s(new (std::nothrow) sg_fill);
+  SG_REQUIRE(s != nullptr, "sg_fill_create: out of host memory");
+  s->V = V;
+  s->F = F;
+  SG_HIP_TRY(s->loop_ptr.alloc(1));
+  SG_HIP_TRY(hipMemsetAsync(s->loop_ptr.p, 0, sizeof(int64_t), stream));
+  if (F == 0) {
+    SG_HIP_TRY(hipStreamSynchronize(stream));
+    *out = s.release();
+    return SG_OK;
+  }
+
+  DeviceBuf<uint64_t> keys_a, keys_b, picked;
+  DeviceBuf<uint8_t> marks;
+  DeviceBuf<int> count, flags;
+  DeviceBuf<unsigned long long> stats;
+  DeviceBuf<char> temp;
+  int h_flags[2] = {0, 0}, h_count = 0;
+  unsigned long long h_stats[4] = {0, 0, ~0ull, 0};
+  SG_HIP_TRY(keys_a.alloc(n_half));
+  SG_HIP_TRY(keys_b.alloc(n_half));
+  SG_HIP_TRY(marks.alloc(n_half));
+  SG_HIP_TRY(picked.alloc(n_half));
+  SG_HIP_TRY(count.alloc(1));
+  SG_HIP_TRY(flags.alloc(2));
+  SG_HIP_TRY(stats.alloc(4));
+  SG_HIP_TRY(hipMemsetAsync(flags.p, 0, sizeof(h_flags), stream));
+  SG_HIP_TRY(hipMemcpyAsync(stats.p, h_stats, sizeof(h_stats), hipMemcpyHostToDevice, stream));
+  fill_keys<<<blocks_for(n_half), kThreads, 0, stream>>>(faces, n_half, V, keys_a.p, flags.p);
+  SG_HIP_TRY(hipGetLastError());
+  const int hi_bits = bits_for((uint64_t)V, 31);
+  const uint64_t* sorted = keys_b.p;        // hipCUB's iterator arguments keep the const they had
+  const uint8_t* is_boundary = marks.p;
+  size_t t1 = 0, t2 = 0;
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, keys_a.p, keys_b.p, (int)n_half, 0, 33 + hi_bits, stream));
+  SG_HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, t2, sorted, is_boundary, picked.p, count.p, (int)n_half, stream));
+  const size_t tb = t1 > t2 ? t1 : t2;
+  SG_HIP_TRY(temp.alloc(tb ? tb : 16));
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp.p, t1, keys_a.p, keys_b.p, (int)n_half, 0, 33 + hi_bits, stream));
+  mark_boundary<<<blocks_for(n_half), kThreads, 0, stream>>>(keys_b.p, n_half, marks.p, stats.p);
+  SG_HIP_TRY(hipGetLastError());
+  SG_HIP_TRY(hipcub::DeviceSelect::Flagged(temp.p, t2, sorted, is_boundary, picked.p, count.p, (int)n_half, stream));
+  SG_HIP_TRY(hipMemcpyAsync(&h_count, count.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipStreamSynchronize(stream));
+  SG_REQUIRE(!h_flags[0], "sg_fill_create: face refers to a vertex outside [0, %lld)", (long long)V);
+  SG_REQUIRE(!h_flags[1], "sg_fill_create: degenerate face (repeated vertex)");
+  SG_REQUIRE(h_count >= 0 && h_count <= n_half, "sg_fill_create: boundary count %d out of range", h_count);
+  const int64_t nb = h_count;
+
+  // the boundary half-edges as a << 32 | b, ascending: the sources are then the boundary vertices in ascending order
+  DeviceBuf<uint64_t> bk;
+  DeviceBuf<int32_t> next;
+  if (nb > 0) {
+    SG_HIP_TRY(bk.alloc(nb));
+    SG_HIP_TRY(next.alloc(nb));
+    uint64_t* unsorted = keys_a.p;                      // the full-size buffers are free again
+    directed_from_keys<<<blocks_for(nb), kThreads, 0, stream>>>(picked.p, nb, unsorted);
+    SG_HIP_TRY(hipGetLastError());
+    size_t t3 = 0;
+    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, t3, unsorted, bk.p, (int)nb, 0, 64, stream));
+    DeviceBuf<char> temp3;
+    SG_HIP_TRY(temp3.alloc(t3 ? t3 : 16));
+    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp3.p, t3, unsorted, bk.p, (int)nb, 0, 64, stream));
+    SG_HIP_TRY(hipMemsetAsync(next.p, 0xff, (size_t)nb * sizeof(int32_t), stream));
+    link_boundary<<<blocks_for(nb), kThreads, 0, stream>>>(bk.p, nb, next.p, stats.p);
+    check_links<<<blocks_for(nb), kThreads, 0, stream>>>(next.p, nb, stats.p);
+    SG_HIP_TRY(hipGetLastError());
+    SG_HIP_TRY(hipStreamSynchronize(stream));           // temp3 is freed here
+  }
+  SG_HIP_TRY(hipMemcpyAsync(h_stats, stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipStreamSynchronize(stream));
+  s->n_dup = (int64_t)h_stats[0];
+  s->n_bow = (int64_t)h_stats[1];
+  if (s->n_dup || s->n_bow) {                           // unorderable: reported by sg_fill_query, nothing is walked
+    s->bad_vertex = (int64_t)h_stats[2];
+    *out = s.release();
+    return SG_OK;
+  }
+  SG_REQUIRE(h_stats[3] == 0, "sg_fill_create: the boundary half-edges do not form a permutation (%llu broken links)",
+             h_stats[3]);
+  if (nb == 0) {
+    *out = s.release();
+    return SG_OK;
+  }
+
+  // pointer jumping: after `rounds` rounds the window of every vertex is at least as long as the longest loop can be
+  DeviceBuf<uint64_t> st_a, st_b;
+  DeviceBuf<int32_t> jp_a, jp_b;
+  DeviceBuf<int64_t> heads, loop_of, sizes;
+  SG_HIP_TRY(st_a.alloc(nb));
+  SG_HIP_TRY(st_b.alloc(nb));
+  SG_HIP_TRY(jp_a.alloc(nb));
+  SG_HIP_TRY(jp_b.alloc(nb));
+  SG_HIP_TRY(heads.alloc(nb + 1));
+  SG_HIP_TRY(loop_of.alloc(nb + 1));
+  uint64_t* st = st_a.p;
+  uint64_t* st_o = st_b.p;
+  int32_t* jp = jp_a.p;
+  int32_t* jp_o = jp_b.p;
+  jump_init<<<blocks_for(nb), kThreads, 0, stream>>>(next.p, nb, st, jp);
+  for (uint64_t span = 1; span < (uint64_t)nb; span <<= 1) {
+    jump_round<<<blocks_for(nb), kThreads, 0, stream>>>(st, jp, nb, span, st_o, jp_o);
+    uint64_t* ts = st; st = st_o; st_o = ts;
+    int32_t* tj = jp; jp = jp_o; jp_o = tj;
+  }
+  SG_HIP_TRY(hipGetLastError());
+  SG_HIP_TRY(hipMemsetAsync(heads.p + nb, 0, sizeof(int64_t), stream));
+  loop_heads<<<blocks_for(nb), kThreads, 0, stream>>>(st, nb, heads.p);
+  SG_HIP_TRY(hipGetLastError());
+  if (int rc = exclusive_sum(heads.p, loop_of.p, nb + 1, stream)) return rc;
+  int64_t L = 0;
+  SG_HIP_TRY(hipMemcpyAsync(&L, loop_of.p + nb, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipStreamSynchronize(stream));
+  SG_REQUIRE(L >= 1 && L <= nb, "sg_fill_create: loop count %lld out of range", (long long)L);
+
+  SG_HIP_TRY(sizes.alloc(L + 1));
+  SG_HIP_TRY(hipMemsetAsync(sizes.p, 0, (size_t)(L + 1) * sizeof(int64_t), stream));
+  loop_sizes<<<blocks_for(nb), kThreads, 0, stream>>>(st, next.p, loop_of.p, nb, L, sizes.p);
+  SG_HIP_TRY(hipGetLastError());
+  SG_HIP_TRY(s->loop_ptr.alloc(L + 1));                 // releases the one-entry table of above
+  SG_HIP_TRY(s->loop_verts.alloc(nb));
+  if (int rc = exclusive_sum(sizes.p, s->loop_ptr.p, L + 1, stream)) return rc;
+  int64_t total = 0;
+  SG_HIP_TRY(hipMemcpyAsync(&total, s->loop_ptr.p + L, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipStreamSynchronize(stream));
+  SG_REQUIRE(total == nb, "sg_fill_create: the loops hold %lld vertices, the boundary %lld", (long long)total, (long long)nb);
+  SG_HIP_TRY(hipMemsetAsync(s->loop_verts.p, 0xff, (size_t)nb * sizeof(int64_t), stream));
+  loop_scatter<<<blocks_for(nb), kThreads, 0, stream>>>(st, next.p, loop_of.p, bk.p, s->loop_ptr.p, nb, L, s->loop_verts.p);
+  SG_HIP_TRY(hipGetLastError());
+  SG_HIP_TRY(hipStreamSynchronize(stream));             // the temporaries are freed on return
+  s->nb = nb;
+  s->L = L;
+  *out = s.release();
+  return SG_OK;
+}
+
+int fill_plan(sg_fill* s, int64_t max_hole_edges, hipStream_t stream, int64_t* n_new_vertices, int64_t* n_new_faces) {
+  SG_REQUIRE(!s->n_dup && !s->n_bow, "sg_fill_plan: the boundary is unorderable (see sg_fill_query)");
+  free_sizes(s);
+  *n_new_vertices = *n_new_faces = 0;
+  if (s->L > 0) {
+    if (int rc = size_patches(s, max_hole_edges, stream)) {
+      free_sizes(s);
+      return rc;
+    }
+  }
   s->planned = true;
-  guard.s = nullptr;
   *n_new_vertices = s->Vn;
   *n_new_faces = s->Fn;
   return SG_OK;
@@ -626,15 +592,15 @@ int fill_emit(sg_fill* s, const float* vs, float* new_vs, int64_t* new_faces, ui
   if (L == 0) return SG_OK;
   SG_REQUIRE(filled_out != nullptr && vs != nullptr, "sg_fill_emit: null pointer");
   SG_REQUIRE((s->Vn == 0 || new_vs) && (s->Fn == 0 || new_faces), "sg_fill_emit: null pointer");
-  SG_HIP_TRY(hipMemcpyAsync(filled_out, s->filled, (size_t)L, hipMemcpyDeviceToDevice, stream));
+  SG_HIP_TRY(hipMemcpyAsync(filled_out, s->filled.p, (size_t)L, hipMemcpyDeviceToDevice, stream));
   if (s->Vn > 0) {
-    loop_geometry<<<(unsigned)L, kThreads, 0, stream>>>(vs, s->loop_ptr, s->loop_verts, s->filled, s->cum, s->geo);
-    emit_vertices<<<blocks_for(s->Vn), kThreads, 0, stream>>>(vs, s->loop_ptr, s->loop_verts, L, s->base, s->base + 2 * W,
-                                                             s->ring_v, s->cum, s->geo, s->Vn, new_vs);
+    loop_geometry<<<(unsigned)L, kThreads, 0, stream>>>(vs, s->loop_ptr.p, s->loop_verts.p, s->filled.p, s->cum.p, s->geo.p);
+    emit_vertices<<<blocks_for(s->Vn), kThreads, 0, stream>>>(vs, s->loop_ptr.p, s->loop_verts.p, L, s->base.p, s->base.p + 2 * W,
+                                                             s->ring_v.p, s->cum.p, s->geo.p, s->Vn, new_vs);
   }
   if (s->Fn > 0)
-    emit_faces<<<blocks_for(s->Fn), kThreads, 0, stream>>>(s->loop_ptr, s->loop_verts, L, s->V, s->base, s->base + W,
-                                                          s->base + 2 * W, s->ring_v, s->ring_f, s->Fn, new_faces);
+    emit_faces<<<blocks_for(s->Fn), kThreads, 0, stream>>>(s->loop_ptr.p, s->loop_verts.p, L, s->V, s->base.p, s->base.p + W,
+                                                          s->base.p + 2 * W, s->ring_v.p, s->ring_f.p, s->Fn, new_faces);
   SG_HIP_TRY(hipGetLastError());
   return SG_OK;
 }
@@ -652,9 +618,9 @@ void fill_query(const sg_fill* s, int64_t* info) {
 
 int fill_loops(const sg_fill* s, int64_t* loop_ptr_out, int64_t* loop_verts_out, hipStream_t stream) {
   SG_REQUIRE(!s->n_dup && !s->n_bow, "sg_fill_loops: the boundary is unorderable (see sg_fill_query)");
-  SG_HIP_TRY(hipMemcpyAsync(loop_ptr_out, s->loop_ptr, (size_t)(s->L + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
+  SG_HIP_TRY(hipMemcpyAsync(loop_ptr_out, s->loop_ptr.p, (size_t)(s->L + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
   if (s->nb > 0)
-    SG_HIP_TRY(hipMemcpyAsync(loop_verts_out, s->loop_verts, (size_t)s->nb * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
+    SG_HIP_TRY(hipMemcpyAsync(loop_verts_out, s->loop_verts.p, (size_t)s->nb * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
   return SG_OK;
 }
 

@@ -24,17 +24,12 @@
 //
 // Bound: the latency of the dependent node loads, as in surface_query; the float64 arithmetic only runs on candidates whose
 // boxes overlap the face's.  Per candidate: 4 bytes of tri[] (the id), 24 bytes of faces, 36 bytes of vs.
-#include <hipcub/hipcub.hpp>
-
-#include "mesh_bvh.h"
+#include "mesh_bvh.h"   // struct sg_surface, kLeaf, kStack, the child codes; mesh_common.h
 
 namespace sg {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kSelfThreads = 64;   // one wavefront per workgroup: its stack is 64 x 64 int32 = 16 KiB of LDS
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 struct D3 {
   double x, y, z;
@@ -283,21 +278,6 @@ __global__ void split_keys(const uint64_t* __restrict__ keys, int64_t n, int64_t
   pairs[2 * p + 1] = (int64_t)(k & 0xffffffffull);
 }
 
-// Stream-ordered temporaries: no host synchronisation to free them.
-struct AsyncBuf {
-  void* p = nullptr;
-  hipStream_t s = nullptr;
-  explicit AsyncBuf(hipStream_t st) : s(st) {}
-  hipError_t alloc(size_t bytes) { return hipMallocAsync(&p, bytes ? bytes : 16, s); }
-  ~AsyncBuf() { if (p) (void)hipFreeAsync(p, s); }
-};
-
-int bits_for(uint64_t n) {
-  int b = 1;
-  while (b < 63 && (n >> b) != 0) ++b;
-  return b;
-}
-
 // what both entry points check before anything touches the device; *empty: nothing to do
 int check_common(const char* who, const sg_surface* s, const float* vs, const int64_t* faces, int64_t F, bool* empty) {
   *empty = false;
@@ -328,7 +308,7 @@ SG_API int sg_surface_self_count(const sg_surface* s, const float* vs, const int
   SG_HIP_TRY(hipMemsetAsync(n_any, 0, (size_t)F * sizeof(int32_t), stream));
   SG_HIP_TRY(hipMemsetAsync(stats_dev, 0, 2 * sizeof(int64_t), stream));
   const int64_t nb = (F + kSelfThreads - 1) / kSelfThreads;
-  self_overlap<false><<<(unsigned)nb, kSelfThreads, 0, stream>>>(s->nodes, s->tri, F, s->V, vs, faces, n_any, n_upper,
+  self_overlap<false><<<(unsigned)nb, kSelfThreads, 0, stream>>>(s->nodes.p, s->tri.p, F, s->V, vs, faces, n_any, n_upper,
                                                                 (unsigned long long*)stats_dev, nullptr, 0, nullptr);
   SG_HIP_TRY(hipGetLastError());
   return SG_OK;
@@ -343,22 +323,21 @@ SG_API int sg_surface_self_pairs(const sg_surface* s, const float* vs, const int
   if (empty || n_pairs == 0) return SG_OK;
   SG_REQUIRE(offsets && pairs, "sg_surface_self_pairs: null pointer");
   hipStream_t stream = (hipStream_t)stream_;
-  AsyncBuf keys_a(stream), keys_b(stream), temp(stream);
-  SG_HIP_TRY(keys_a.alloc((size_t)n_pairs * sizeof(uint64_t)));
-  SG_HIP_TRY(keys_b.alloc((size_t)n_pairs * sizeof(uint64_t)));
+  AsyncBuf<uint64_t> keys_a(stream), keys_b(stream);
+  AsyncBuf<char> temp(stream);
+  SG_HIP_TRY(keys_a.alloc(n_pairs));
+  SG_HIP_TRY(keys_b.alloc(n_pairs));
   SG_HIP_TRY(hipMemsetAsync(keys_a.p, 0, (size_t)n_pairs * sizeof(uint64_t), stream));   // offsets that leave a gap: (0, 0) rows
   const int64_t nb = (F + kSelfThreads - 1) / kSelfThreads;
-  self_overlap<true><<<(unsigned)nb, kSelfThreads, 0, stream>>>(s->nodes, s->tri, F, s->V, vs, faces, nullptr, nullptr, nullptr,
-                                                               offsets, n_pairs, (uint64_t*)keys_a.p);
+  self_overlap<true><<<(unsigned)nb, kSelfThreads, 0, stream>>>(s->nodes.p, s->tri.p, F, s->V, vs, faces, nullptr, nullptr,
+                                                               nullptr, offsets, n_pairs, keys_a.p);
   SG_HIP_TRY(hipGetLastError());
-  const int end_bit = 32 + bits_for((uint64_t)F);
+  const int end_bit = 32 + bits_for((uint64_t)F, 63);
   size_t tb = 0;
-  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p, (int)n_pairs, 0,
-                                               end_bit, stream));
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, keys_a.p, keys_b.p, (int)n_pairs, 0, end_bit, stream));
   SG_HIP_TRY(temp.alloc(tb));
-  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp.p, tb, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p, (int)n_pairs, 0,
-                                               end_bit, stream));
-  split_keys<<<blocks_for(n_pairs), kThreads, 0, stream>>>((const uint64_t*)keys_b.p, n_pairs, pairs);
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp.p, tb, keys_a.p, keys_b.p, (int)n_pairs, 0, end_bit, stream));
+  split_keys<<<blocks_for(n_pairs), kThreads, 0, stream>>>(keys_b.p, n_pairs, pairs);
   SG_HIP_TRY(hipGetLastError());
   return SG_OK;
 }

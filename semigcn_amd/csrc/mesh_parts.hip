@@ -33,35 +33,25 @@
 // even a stale root is corrected by the value the failed CAS brings back from memory.
 //
 // All of it is integer work bound by the sort and by scattered 4-byte accesses.
-#include <hipcub/hipcub.hpp>
-
-#include <initializer_list>
+#include <memory>
 #include <new>
 
-#include "sg_common.h"
+#include "mesh_common.h"
 
 struct sg_parts {
   int64_t V = 0, F = 0, K = 0, n_degenerate = 0, largest = -1, largest_count = 0;
-  int32_t* tri = nullptr;          // [F][3] the faces as int32: select and emit run on the plan's own copy
-  int32_t* label = nullptr;        // [F] component of every face, -1 = degenerate
-  int64_t* count = nullptr;        // [K] faces per component
+  sg::DeviceBuf<int32_t> tri;      // [F][3] the faces as int32: select and emit run on the plan's own copy
+  sg::DeviceBuf<int32_t> label;    // [F] component of every face, -1 = degenerate
+  sg::DeviceBuf<unsigned long long> count;   // [K] faces per component (the callers' int64, as atomicAdd takes it)
   bool selected = false;
   int64_t Vk = 0, Fk = 0;
-  int32_t* flags = nullptr;        // [F + 1] face kept, then [V + 1] vertex kept (the last entry of each is 0)
-  int32_t* new_id = nullptr;       // their exclusive scans, same layout: the new ids, and the totals in the last entries
+  sg::DeviceBuf<int32_t> flags;    // [F + 1] face kept, then [V + 1] vertex kept (the last entry of each is 0)
+  sg::DeviceBuf<int32_t> new_id;   // their exclusive scans, same layout: the new ids, and the totals in the last entries
 };
+static_assert(sizeof(unsigned long long) == sizeof(int64_t), "sg_parts::count is cleared and copied out as int64");
 
 namespace sg {
 namespace {
-
-constexpr int kThreads = 256;
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-struct DeviceBuf {
-  void* p = nullptr;
-  ~DeviceBuf() { if (p) (void)hipFree(p); }
-};
 
 // ---- union-find ------------------------------------------------------------------------------------------------------
 __device__ inline int32_t load_parent(const int32_t* p) {
@@ -141,7 +131,7 @@ __global__ void edge_keys(const int32_t* __restrict__ tri, const uint8_t* __rest
   const int i = (int)(h - 3 * f);
   uint64_t key = ~0ull;
   if (!degen[f]) {
-    const int64_t a = tri[3 * f + i], b = tri[3 * f + (i == 2 ? 0 : i + 1)];
+    const int64_t a = tri[3 * f + i], b = tri[3 * f + next3(i)];
     key = (uint64_t)(a < b ? a : b) * (uint64_t)V + (uint64_t)(a < b ? b : a);
   }
   keys[h] = key;
@@ -211,11 +201,6 @@ __global__ void largest_component(const unsigned long long* __restrict__ count, 
   atomicMax(best, (count[k] << 32) | (unsigned long long)(0xffffffffu - (uint32_t)k));
 }
 
-__global__ void widen_labels(const int32_t* __restrict__ label, int64_t F, int64_t* __restrict__ out) {
-  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (f < F) out[f] = label[f];
-}
-
 // ---- select and emit ---------------------------------------------------------------------------------------------------
 // vflag was zeroed; every thread that marks a vertex writes the same 1
 __global__ void mark_kept(const int32_t* __restrict__ tri, const int32_t* __restrict__ label, const uint8_t* __restrict__ keep,
@@ -262,117 +247,92 @@ __global__ void emit_kept_faces(const int32_t* __restrict__ tri, const int32_t* 
   face_ids[n] = f;
 }
 
-int exclusive_sum32(const int32_t* in, int32_t* out, int64_t n, hipStream_t stream) {
-  size_t tb = 0;
-  SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, stream));
-  DeviceBuf temp;
-  SG_HIP_TRY(hipMalloc(&temp.p, tb ? tb : 16));
-  SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(temp.p, tb, in, out, (int)n, stream));
-  SG_HIP_TRY(hipStreamSynchronize(stream));     // the temporary is freed on return
-  return SG_OK;
-}
-
 }  // namespace
 
-void destroy_parts(sg_parts* s) {
-  if (!s) return;
-  for (void* p : {(void*)s->tri, (void*)s->label, (void*)s->count, (void*)s->flags, (void*)s->new_id})
-    if (p) (void)hipFree(p);
-  delete s;
-}
+void destroy_parts(sg_parts* s) { delete s; }
 
 int parts_create(const int64_t* faces, int64_t F, int64_t V, int connectivity, hipStream_t stream, sg_parts** out) {
   const int64_t n_half = 3 * F;
   SG_REQUIRE(V < ((int64_t)1 << 31) && n_half < ((int64_t)1 << 31), "sg_parts_create: sizes must fit int32");
-  sg_parts* s = new (std::nothrow) sg_parts;
+  std::unique_ptr<sg_parts> s(new (std::nothrow) sg_parts);
   SG_REQUIRE(s != nullptr, "sg_parts_create: out of host memory");
-  struct Guard {
-    sg_parts* s;
-    ~Guard() { destroy_parts(s); }
-  } guard{s};
   s->V = V;
   s->F = F;
   if (F == 0) {
-    guard.s = nullptr;
-    *out = s;
+    *out = s.release();
     return SG_OK;
   }
 
-  DeviceBuf degen, flags, stats, parent, slot, rep, is_rep, rank;
+  DeviceBuf<uint8_t> degen;
+  DeviceBuf<int> flags;
+  DeviceBuf<unsigned long long> stats;
+  DeviceBuf<int32_t> parent, slot, rep, is_rep, rank;
   int h_flags[1] = {0};
   unsigned long long h_stats[2] = {0, 0};                  // degenerate faces; the largest component, packed
   const int64_t n_nodes = connectivity == 0 ? F : V;
-  SG_HIP_TRY(hipMalloc(&degen.p, (size_t)F));
-  SG_HIP_TRY(hipMalloc(&flags.p, sizeof(h_flags)));
-  SG_HIP_TRY(hipMalloc(&stats.p, sizeof(h_stats)));
-  SG_HIP_TRY(hipMalloc(&parent.p, (size_t)(n_nodes > 0 ? n_nodes : 1) * sizeof(int32_t)));
-  SG_HIP_TRY(hipMalloc(&rep.p, (size_t)F * sizeof(int32_t)));
-  SG_HIP_TRY(hipMalloc(&is_rep.p, (size_t)(F + 1) * sizeof(int32_t)));
-  SG_HIP_TRY(hipMalloc(&rank.p, (size_t)(F + 1) * sizeof(int32_t)));
-  SG_HIP_TRY(hipMalloc(&s->label, (size_t)F * sizeof(int32_t)));
-  SG_HIP_TRY(hipMalloc(&s->tri, (size_t)n_half * sizeof(int32_t)));
+  SG_HIP_TRY(degen.alloc(F));
+  SG_HIP_TRY(flags.alloc(1));
+  SG_HIP_TRY(stats.alloc(2));
+  SG_HIP_TRY(parent.alloc(n_nodes));
+  SG_HIP_TRY(rep.alloc(F));
+  SG_HIP_TRY(is_rep.alloc(F + 1));
+  SG_HIP_TRY(rank.alloc(F + 1));
+  SG_HIP_TRY(s->label.alloc(F));
+  SG_HIP_TRY(s->tri.alloc(n_half));
   SG_HIP_TRY(hipMemsetAsync(flags.p, 0, sizeof(h_flags), stream));
   SG_HIP_TRY(hipMemsetAsync(stats.p, 0, sizeof(h_stats), stream));
-  classify_faces<<<blocks_for(F), kThreads, 0, stream>>>(faces, F, V, s->tri, (uint8_t*)degen.p, (int*)flags.p,
-                                                        (unsigned long long*)stats.p);
+  classify_faces<<<blocks_for(F), kThreads, 0, stream>>>(faces, F, V, s->tri.p, degen.p, flags.p, stats.p);
   SG_HIP_TRY(hipGetLastError());
   // the unions below index by vertex: nothing runs on ids that were not checked
   SG_HIP_TRY(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, stream));
   SG_HIP_TRY(hipStreamSynchronize(stream));
   SG_REQUIRE(!h_flags[0], "sg_parts_create: face refers to a vertex outside [0, %lld)", (long long)V);
 
-  int32_t* d_parent = (int32_t*)parent.p;
-  if (n_nodes > 0) iota32<<<blocks_for(n_nodes), kThreads, 0, stream>>>(d_parent, n_nodes);
+  if (n_nodes > 0) iota32<<<blocks_for(n_nodes), kThreads, 0, stream>>>(parent.p, n_nodes);
   SG_HIP_TRY(hipGetLastError());
   if (connectivity == 0) {
-    DeviceBuf keys_a, keys_b, vals_a, vals_b, temp;
-    SG_HIP_TRY(hipMalloc(&keys_a.p, (size_t)n_half * sizeof(uint64_t)));
-    SG_HIP_TRY(hipMalloc(&keys_b.p, (size_t)n_half * sizeof(uint64_t)));
-    SG_HIP_TRY(hipMalloc(&vals_a.p, (size_t)n_half * sizeof(int32_t)));
-    SG_HIP_TRY(hipMalloc(&vals_b.p, (size_t)n_half * sizeof(int32_t)));
-    edge_keys<<<blocks_for(n_half), kThreads, 0, stream>>>(s->tri, (const uint8_t*)degen.p, n_half, V, (uint64_t*)keys_a.p,
-                                                          (int32_t*)vals_a.p);
+    DeviceBuf<uint64_t> keys_a, keys_b;
+    DeviceBuf<int32_t> vals_a, vals_b;
+    DeviceBuf<char> temp;
+    SG_HIP_TRY(keys_a.alloc(n_half));
+    SG_HIP_TRY(keys_b.alloc(n_half));
+    SG_HIP_TRY(vals_a.alloc(n_half));
+    SG_HIP_TRY(vals_b.alloc(n_half));
+    edge_keys<<<blocks_for(n_half), kThreads, 0, stream>>>(s->tri.p, degen.p, n_half, V, keys_a.p, vals_a.p);
     SG_HIP_TRY(hipGetLastError());
-    int bits = 1;                                          // the keys are below V * V < 2^62; ~0 has every sorted bit set
-    while (bits < 62 && (((uint64_t)V * (uint64_t)V) >> bits) != 0) ++bits;
+    const int bits = bits_for((uint64_t)V * (uint64_t)V, 62);   // the keys are below V * V < 2^62; ~0 has every sorted bit set
     size_t tb = 0;
-    SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p,
-                                                  (const int32_t*)vals_a.p, (int32_t*)vals_b.p, (int)n_half, 0, bits, stream));
-    SG_HIP_TRY(hipMalloc(&temp.p, tb ? tb : 16));
-    SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p,
-                                                  (const int32_t*)vals_a.p, (int32_t*)vals_b.p, (int)n_half, 0, bits, stream));
-    union_sorted_edges<<<blocks_for(n_half), kThreads, 0, stream>>>((const uint64_t*)keys_b.p, (const int32_t*)vals_b.p, n_half, F,
-                                                                   d_parent);
+    SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_a.p, keys_b.p, vals_a.p, vals_b.p, (int)n_half, 0, bits,
+                                                  stream));
+    SG_HIP_TRY(temp.alloc(tb ? tb : 16));
+    SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys_a.p, keys_b.p, vals_a.p, vals_b.p, (int)n_half, 0, bits,
+                                                  stream));
+    union_sorted_edges<<<blocks_for(n_half), kThreads, 0, stream>>>(keys_b.p, vals_b.p, n_half, F, parent.p);
     SG_HIP_TRY(hipGetLastError());
-    flatten<<<blocks_for(F), kThreads, 0, stream>>>(d_parent, F);
-    representatives<<<blocks_for(F + 1), kThreads, 0, stream>>>(s->tri, (const uint8_t*)degen.p, F, d_parent, nullptr, nullptr,
-                                                               (int32_t*)rep.p, (int32_t*)is_rep.p);
+    flatten<<<blocks_for(F), kThreads, 0, stream>>>(parent.p, F);
+    representatives<<<blocks_for(F + 1), kThreads, 0, stream>>>(s->tri.p, degen.p, F, parent.p, nullptr, nullptr, rep.p, is_rep.p);
     SG_HIP_TRY(hipGetLastError());
     SG_HIP_TRY(hipStreamSynchronize(stream));              // the sort's buffers are freed here
   } else {
-    SG_HIP_TRY(hipMalloc(&slot.p, (size_t)(V > 0 ? V : 1) * sizeof(int32_t)));
+    SG_HIP_TRY(slot.alloc(V));
     SG_HIP_TRY(hipMemsetAsync(slot.p, 0x7f, (size_t)(V > 0 ? V : 1) * sizeof(int32_t), stream));   // 0x7f7f7f7f > any face
-    union_face_vertices<<<blocks_for(2 * F), kThreads, 0, stream>>>(s->tri, (const uint8_t*)degen.p, F, d_parent);
+    union_face_vertices<<<blocks_for(2 * F), kThreads, 0, stream>>>(s->tri.p, degen.p, F, parent.p);
     SG_HIP_TRY(hipGetLastError());
-    if (V > 0) flatten<<<blocks_for(V), kThreads, 0, stream>>>(d_parent, V);
-    min_face_of_root<<<blocks_for(F), kThreads, 0, stream>>>(s->tri, (const uint8_t*)degen.p, F, d_parent, (int32_t*)slot.p);
-    representatives<<<blocks_for(F + 1), kThreads, 0, stream>>>(s->tri, (const uint8_t*)degen.p, F, nullptr, d_parent,
-                                                               (const int32_t*)slot.p, (int32_t*)rep.p, (int32_t*)is_rep.p);
+    if (V > 0) flatten<<<blocks_for(V), kThreads, 0, stream>>>(parent.p, V);
+    min_face_of_root<<<blocks_for(F), kThreads, 0, stream>>>(s->tri.p, degen.p, F, parent.p, slot.p);
+    representatives<<<blocks_for(F + 1), kThreads, 0, stream>>>(s->tri.p, degen.p, F, nullptr, parent.p, slot.p, rep.p, is_rep.p);
     SG_HIP_TRY(hipGetLastError());
   }
-  if (int rc = exclusive_sum32((const int32_t*)is_rep.p, (int32_t*)rank.p, F + 1, stream)) return rc;
+  if (int rc = exclusive_sum(is_rep.p, rank.p, F + 1, stream)) return rc;
   int32_t K32 = 0;
-  SG_HIP_TRY(hipMemcpyAsync(&K32, (int32_t*)rank.p + F, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipMemcpyAsync(&K32, rank.p + F, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   SG_HIP_TRY(hipStreamSynchronize(stream));
   const int64_t K = K32;
   SG_REQUIRE(K >= 0 && K <= F, "sg_parts_create: component count %lld out of range", (long long)K);
-  SG_HIP_TRY(hipMalloc(&s->count, (size_t)(K > 0 ? K : 1) * sizeof(int64_t)));
-  SG_HIP_TRY(hipMemsetAsync(s->count, 0, (size_t)(K > 0 ? K : 1) * sizeof(int64_t), stream));
-  gather_labels<<<blocks_for(F), kThreads, 0, stream>>>((const int32_t*)rep.p, (const int32_t*)rank.p, F, K, s->label,
-                                                       (unsigned long long*)s->count);
-  if (K > 0)
-    largest_component<<<blocks_for(K), kThreads, 0, stream>>>((const unsigned long long*)s->count, K,
-                                                             (unsigned long long*)stats.p + 1);
+  SG_HIP_TRY(s->count.alloc(K));
+  SG_HIP_TRY(hipMemsetAsync(s->count.p, 0, (size_t)(K > 0 ? K : 1) * sizeof(int64_t), stream));
+  gather_labels<<<blocks_for(F), kThreads, 0, stream>>>(rep.p, rank.p, F, K, s->label.p, s->count.p);
+  if (K > 0) largest_component<<<blocks_for(K), kThreads, 0, stream>>>(s->count.p, K, stats.p + 1);
   SG_HIP_TRY(hipGetLastError());
   SG_HIP_TRY(hipMemcpyAsync(h_stats, stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, stream));
   SG_HIP_TRY(hipStreamSynchronize(stream));                // the temporaries are freed on return
@@ -383,8 +343,7 @@ int parts_create(const int64_t* faces, int64_t F, int64_t V, int connectivity, h
     s->largest_count = (int64_t)(h_stats[1] >> 32);
     SG_REQUIRE(s->largest >= 0 && s->largest < K, "sg_parts_create: largest component %lld out of range", (long long)s->largest);
   }
-  guard.s = nullptr;
-  *out = s;
+  *out = s.release();
   return SG_OK;
 }
 
@@ -401,9 +360,9 @@ void parts_query(const sg_parts* s, int64_t* info) {
 
 int parts_labels(const sg_parts* s, int64_t* face_label, int64_t* face_count, hipStream_t stream) {
   SG_REQUIRE((s->F == 0 || face_label) && (s->K == 0 || face_count), "sg_parts_labels: null pointer");
-  if (s->F > 0) widen_labels<<<blocks_for(s->F), kThreads, 0, stream>>>(s->label, s->F, face_label);
+  if (s->F > 0) widen32<<<blocks_for(s->F), kThreads, 0, stream>>>(s->label.p, s->F, face_label);
   SG_HIP_TRY(hipGetLastError());
-  if (s->K > 0) SG_HIP_TRY(hipMemcpyAsync(face_count, s->count, (size_t)s->K * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
+  if (s->K > 0) SG_HIP_TRY(hipMemcpyAsync(face_count, s->count.p, (size_t)s->K * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
   return SG_OK;
 }
 
@@ -412,20 +371,20 @@ int parts_select(sg_parts* s, const uint8_t* keep, hipStream_t stream, int64_t* 
   const int64_t F = s->F, V = s->V, n = (F + 1) + (V + 1);
   s->selected = false;
   *n_vertices = *n_faces = 0;
-  if (!s->flags) {
-    SG_HIP_TRY(hipMalloc(&s->flags, (size_t)n * sizeof(int32_t)));
-    SG_HIP_TRY(hipMalloc(&s->new_id, (size_t)n * sizeof(int32_t)));
+  if (!s->flags.p) {
+    SG_HIP_TRY(s->flags.alloc(n));
+    SG_HIP_TRY(s->new_id.alloc(n));
   }
-  int32_t* fflag = s->flags;
-  int32_t* vflag = s->flags + (F + 1);
+  int32_t* fflag = s->flags.p;
+  int32_t* vflag = s->flags.p + (F + 1);
   SG_HIP_TRY(hipMemsetAsync(vflag, 0, (size_t)(V + 1) * sizeof(int32_t), stream));
-  mark_kept<<<blocks_for(F + 1), kThreads, 0, stream>>>(s->tri, s->label, keep, F, V, s->K, fflag, vflag);
+  mark_kept<<<blocks_for(F + 1), kThreads, 0, stream>>>(s->tri.p, s->label.p, keep, F, V, s->K, fflag, vflag);
   SG_HIP_TRY(hipGetLastError());
-  if (int rc = exclusive_sum32(fflag, s->new_id, F + 1, stream)) return rc;
-  if (int rc = exclusive_sum32(vflag, s->new_id + (F + 1), V + 1, stream)) return rc;
+  if (int rc = exclusive_sum(fflag, s->new_id.p, F + 1, stream)) return rc;
+  if (int rc = exclusive_sum(vflag, s->new_id.p + (F + 1), V + 1, stream)) return rc;
   int32_t totals[2] = {0, 0};
-  SG_HIP_TRY(hipMemcpyAsync(&totals[0], s->new_id + F, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  SG_HIP_TRY(hipMemcpyAsync(&totals[1], s->new_id + (F + 1) + V, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipMemcpyAsync(&totals[0], s->new_id.p + F, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipMemcpyAsync(&totals[1], s->new_id.p + (F + 1) + V, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   SG_HIP_TRY(hipStreamSynchronize(stream));
   SG_REQUIRE(totals[0] >= 0 && totals[0] <= F && totals[1] >= 0 && totals[1] <= V, "sg_parts_select: totals out of range");
   s->Fk = totals[0];
@@ -441,11 +400,11 @@ int parts_emit(sg_parts* s, const float* vs, float* new_vs, int64_t* new_faces, 
   SG_REQUIRE(s->selected, "sg_parts_emit: call sg_parts_select first");
   SG_REQUIRE((s->Vk == 0 || (vs && new_vs && vertex_ids)) && (s->Fk == 0 || (new_faces && face_ids)), "sg_parts_emit: null pointer");
   const int64_t F = s->F, V = s->V;
-  const int32_t* vnew = s->new_id + (F + 1);
+  const int32_t* vnew = s->new_id.p + (F + 1);
   if (s->Vk > 0)
-    emit_kept_vertices<<<blocks_for(V), kThreads, 0, stream>>>(vs, s->flags + (F + 1), vnew, V, s->Vk, new_vs, vertex_ids);
+    emit_kept_vertices<<<blocks_for(V), kThreads, 0, stream>>>(vs, s->flags.p + (F + 1), vnew, V, s->Vk, new_vs, vertex_ids);
   if (s->Fk > 0)
-    emit_kept_faces<<<blocks_for(F), kThreads, 0, stream>>>(s->tri, s->flags, s->new_id, vnew, F, s->Fk, new_faces, face_ids);
+    emit_kept_faces<<<blocks_for(F), kThreads, 0, stream>>>(s->tri.p, s->flags.p, s->new_id.p, vnew, F, s->Fk, new_faces, face_ids);
   SG_HIP_TRY(hipGetLastError());
   return SG_OK;
 }

@@ -10,21 +10,10 @@
 //     three vertices is dropped ((f2v_mat @ (1 - vmask)) == 0).
 // All of it is integer work bound by HBM traffic: half-edges are radix-sorted by (lo, hi) key
 // (hipCUB), masks travel as one bit per mask packed into 64-bit words.
-#include <hipcub/hipcub.hpp>
-
-#include "sg_common.h"
+#include "mesh_common.h"
 
 namespace sg {
 namespace {
-
-constexpr int kThreads = 256;
-
-inline int blocks_for(int64_t n) { return (int)((n + kThreads - 1) / kThreads); }
-
-struct DeviceBuf {
-  void* p = nullptr;
-  ~DeviceBuf() { if (p) (void)hipFree(p); }
-};
 
 // Half-edge h = 3 f + i joins faces[f][i] and faces[f][(i+1)%3]  (util/mesh.py:72-74).
 // flags[0]: vertex id out of range; flags[1]: degenerate face (repeated vertex).
@@ -34,7 +23,7 @@ __global__ void half_edge_keys(const int64_t* __restrict__ faces, int64_t n_half
   if (h >= n_half) return;
   const int64_t f = h / 3;
   const int i = (int)(h - 3 * f);
-  const int64_t a = faces[3 * f + i], b = faces[3 * f + (i == 2 ? 0 : i + 1)];
+  const int64_t a = faces[3 * f + i], b = faces[3 * f + next3(i)];
   uint64_t key = ~0ull;
   if (a < 0 || a >= V || b < 0 || b >= V) {
     flags[0] = 1;
@@ -85,7 +74,7 @@ __global__ void edges_from_heads(const uint32_t* __restrict__ first_half, int64_
   if (e >= n_edges) return;
   const int64_t h = first_half[e], f = h / 3;
   const int i = (int)(h - 3 * f);
-  const int64_t a = faces[3 * f + i], b = faces[3 * f + (i == 2 ? 0 : i + 1)];
+  const int64_t a = faces[3 * f + i], b = faces[3 * f + next3(i)];
   edges[2 * e] = a < b ? a : b;       // tuple(sorted(edge)), util/mesh.py:76
   edges[2 * e + 1] = a < b ? b : a;
 }
@@ -128,45 +117,41 @@ int mesh_edges(const int64_t* faces, int64_t F, int64_t V, int64_t* edges_out, i
   *n_edges_out = 0;
   if (manifold_out) *manifold_out = 1;
   if (F == 0) return SG_OK;
-  DeviceBuf keys_a, keys_b, half_a, half_b, heads, first, first_sorted, count, flags, temp;
-  SG_HIP_TRY(hipMalloc(&keys_a.p, n_half * sizeof(uint64_t)));
-  SG_HIP_TRY(hipMalloc(&keys_b.p, n_half * sizeof(uint64_t)));
-  SG_HIP_TRY(hipMalloc(&half_a.p, n_half * sizeof(uint32_t)));
-  SG_HIP_TRY(hipMalloc(&half_b.p, n_half * sizeof(uint32_t)));
-  SG_HIP_TRY(hipMalloc(&heads.p, n_half));
-  SG_HIP_TRY(hipMalloc(&first.p, n_half * sizeof(uint32_t)));
-  SG_HIP_TRY(hipMalloc(&first_sorted.p, n_half * sizeof(uint32_t)));
-  SG_HIP_TRY(hipMalloc(&count.p, sizeof(int)));
-  SG_HIP_TRY(hipMalloc(&flags.p, 3 * sizeof(int)));
+  DeviceBuf<uint64_t> keys_a, keys_b;
+  DeviceBuf<uint32_t> half_a, half_b, first, first_sorted;
+  DeviceBuf<uint8_t> heads;
+  DeviceBuf<int> count, flags;
+  DeviceBuf<char> temp;
+  SG_HIP_TRY(keys_a.alloc(n_half));
+  SG_HIP_TRY(keys_b.alloc(n_half));
+  SG_HIP_TRY(half_a.alloc(n_half));
+  SG_HIP_TRY(half_b.alloc(n_half));
+  SG_HIP_TRY(heads.alloc(n_half));
+  SG_HIP_TRY(first.alloc(n_half));
+  SG_HIP_TRY(first_sorted.alloc(n_half));
+  SG_HIP_TRY(count.alloc(1));
+  SG_HIP_TRY(flags.alloc(3));
   SG_HIP_TRY(hipMemsetAsync(flags.p, 0, 3 * sizeof(int), stream));
-  half_edge_keys<<<blocks_for(n_half), kThreads, 0, stream>>>(faces, n_half, V, (uint64_t*)keys_a.p,
-                                                             (uint32_t*)half_a.p, (int*)flags.p);
+  half_edge_keys<<<blocks_for(n_half), kThreads, 0, stream>>>(faces, n_half, V, keys_a.p, half_a.p, flags.p);
   SG_HIP_TRY(hipGetLastError());
 
-  int hi_bits = 1;
-  while (hi_bits < 32 && ((uint64_t)V >> hi_bits) != 0) ++hi_bits;
-  int idx_bits = 1;
-  while (idx_bits < 32 && ((uint64_t)n_half >> idx_bits) != 0) ++idx_bits;
+  const int hi_bits = bits_for((uint64_t)V, 32), idx_bits = bits_for((uint64_t)n_half, 32);
+  const uint32_t* half_sorted = half_b.p;     // hipCUB's iterator arguments keep the const they had
+  const uint8_t* is_head = heads.p;
   size_t t1 = 0, t2 = 0, t3 = 0;
-  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p,
-                                                (const uint32_t*)half_a.p, (uint32_t*)half_b.p, (int)n_half, 0,
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, keys_a.p, keys_b.p, half_a.p, half_b.p, (int)n_half, 0,
                                                 32 + hi_bits, stream));
-  SG_HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, t2, (const uint32_t*)half_b.p, (const uint8_t*)heads.p,
-                                           (uint32_t*)first.p, (int*)count.p, (int)n_half, stream));
-  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, t3, (const uint32_t*)first.p, (uint32_t*)first_sorted.p,
-                                               (int)n_half, 0, idx_bits, stream));
+  SG_HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, t2, half_sorted, is_head, first.p, count.p, (int)n_half, stream));
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, t3, first.p, first_sorted.p, (int)n_half, 0, idx_bits, stream));
   size_t tb = t1 > t2 ? t1 : t2;
   if (t3 > tb) tb = t3;
-  SG_HIP_TRY(hipMalloc(&temp.p, tb ? tb : 16));
-  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(temp.p, t1, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p,
-                                                (const uint32_t*)half_a.p, (uint32_t*)half_b.p, (int)n_half, 0,
+  SG_HIP_TRY(temp.alloc(tb ? tb : 16));
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(temp.p, t1, keys_a.p, keys_b.p, half_a.p, half_b.p, (int)n_half, 0,
                                                 32 + hi_bits, stream));
-  scan_runs<<<blocks_for(n_half), kThreads, 0, stream>>>((const uint64_t*)keys_b.p, (const uint32_t*)half_b.p, n_half,
-                                                        (uint8_t*)heads.p, f2f_out, (int*)flags.p);
+  scan_runs<<<blocks_for(n_half), kThreads, 0, stream>>>(keys_b.p, half_b.p, n_half, heads.p, f2f_out, flags.p);
   SG_HIP_TRY(hipGetLastError());
   if (f2f_out) compact_f2f<<<blocks_for(F), kThreads, 0, stream>>>(f2f_out, F);
-  SG_HIP_TRY(hipcub::DeviceSelect::Flagged(temp.p, t2, (const uint32_t*)half_b.p, (const uint8_t*)heads.p,
-                                           (uint32_t*)first.p, (int*)count.p, (int)n_half, stream));
+  SG_HIP_TRY(hipcub::DeviceSelect::Flagged(temp.p, t2, half_sorted, is_head, first.p, count.p, (int)n_half, stream));
   int h_count = 0, h_flags[3] = {0, 0, 0};
   SG_HIP_TRY(hipMemcpyAsync(&h_count, count.p, sizeof(int), hipMemcpyDeviceToHost, stream));
   SG_HIP_TRY(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, stream));
@@ -175,10 +160,8 @@ int mesh_edges(const int64_t* faces, int64_t F, int64_t V, int64_t* edges_out, i
   SG_REQUIRE(!h_flags[1], "sg_mesh_edges: degenerate face (repeated vertex)");
   if (manifold_out) *manifold_out = h_flags[2] ? 0 : 1;
   if (h_count > 0) {
-    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp.p, t3, (const uint32_t*)first.p, (uint32_t*)first_sorted.p,
-                                                 h_count, 0, idx_bits, stream));
-    edges_from_heads<<<blocks_for(h_count), kThreads, 0, stream>>>((const uint32_t*)first_sorted.p, h_count, faces,
-                                                                  edges_out);
+    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp.p, t3, first.p, first_sorted.p, h_count, 0, idx_bits, stream));
+    edges_from_heads<<<blocks_for(h_count), kThreads, 0, stream>>>(first_sorted.p, h_count, faces, edges_out);
     SG_HIP_TRY(hipGetLastError());
     SG_HIP_TRY(hipStreamSynchronize(stream));   // the temporaries are freed on return
   }
@@ -198,10 +181,10 @@ int launch_face_mask(const int64_t* faces, int64_t F, int64_t V, const uint64_t*
                      hipStream_t stream) {
   const int64_t n = F * W;
   if (n == 0) return SG_OK;
-  DeviceBuf bad;
-  SG_HIP_TRY(hipMalloc(&bad.p, sizeof(int)));
+  DeviceBuf<int> bad;
+  SG_HIP_TRY(bad.alloc(1));
   SG_HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(int), stream));
-  face_and_bits<<<blocks_for(n), kThreads, 0, stream>>>(faces, F, V, (int)W, vbits, fbits, (int*)bad.p);
+  face_and_bits<<<blocks_for(n), kThreads, 0, stream>>>(faces, F, V, (int)W, vbits, fbits, bad.p);
   SG_HIP_TRY(hipGetLastError());
   int h_bad = 0;
   SG_HIP_TRY(hipMemcpyAsync(&h_bad, bad.p, sizeof(int), hipMemcpyDeviceToHost, stream));

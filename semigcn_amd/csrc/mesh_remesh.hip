@@ -23,21 +23,14 @@
 // edges never tie and the order in which the atomics arrive cannot matter.  There are no float atomics; integer max and
 // integer sums do not depend on order: every output is deterministic.  The float arithmetic is the squared length, the
 // midpoint and the float64 guard, each a fixed sequence of multiplies and adds: this file is built with -ffp-contract=off.
-#include <hipcub/hipcub.hpp>
-
 #include <initializer_list>
+#include <memory>
 #include <new>
 
-#include "sg_common.h"
+#include "mesh_common.h"
 
 namespace sg {
 namespace {
-
-// a device buffer that only grows; `keep` carries the old bytes over
-struct Buf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
 
 // slots of the counter block
 enum {
@@ -53,40 +46,20 @@ struct sg_remesh {
   unsigned long long h_ctr[sg::kCounters] = {};     // the counters of the creating analysis (validation)
   int64_t bad_key_V = 0;                            // the V that the smallest offending key was formed with
   bool valid = false;
-  sg::Buf vs, par, tri, border;                     // the mesh: float [V][3], int32 [V][2], int32 [F][3], uint8 [V]
-  sg::Buf keys_a, keys_b, vals_a, vals_b, head, incl, he_rank, best, fpos, flag_a, scan_a, flag_f, scan_f, cand, win, slot, val,
-      temp, ctr;
+  sg::GrowBuf<float> vs;                            // the mesh: [V][3]
+  sg::GrowBuf<int32_t> par, tri;                    // [V][2], [F][3]
+  sg::GrowBuf<uint8_t> border;                      // [V]
+  sg::GrowBuf<uint64_t> keys_a, keys_b;
+  sg::GrowBuf<int32_t> vals_a, vals_b, head, incl, he_rank, best, fpos, flag_a, scan_a, flag_f, scan_f, val;
+  sg::GrowBuf<unsigned long long> cand, slot, ctr;
+  sg::GrowBuf<uint8_t> win;
+  sg::GrowBuf<char> temp;
 };
 
 namespace sg {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr float kHalf = 0.5f;
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-int reserve(Buf* b, size_t bytes, bool keep, hipStream_t stream) {
-  if (bytes <= b->cap) return SG_OK;
-  SG_HIP_TRY(hipStreamSynchronize(stream));          // nothing in flight reads what is freed below
-  size_t want = b->cap + b->cap / 2;
-  if (want < bytes) want = bytes;
-  if (want < 256) want = 256;
-  void* q = nullptr;
-  SG_HIP_TRY(hipMalloc(&q, want));
-  if (keep && b->p && b->cap) {
-    hipError_t e = hipMemcpyAsync(q, b->p, b->cap, hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) {
-      (void)hipFree(q);
-      SG_HIP_TRY(e);
-    }
-  }
-  if (b->p) (void)hipFree(b->p);
-  b->p = q;
-  b->cap = want;
-  return SG_OK;
-}
 
 __device__ inline uint32_t hash32(uint32_t x) {
   x ^= x >> 16;
@@ -96,8 +69,6 @@ __device__ inline uint32_t hash32(uint32_t x) {
   x ^= x >> 16;
   return x;
 }
-
-__device__ inline int next3(int k) { return k == 2 ? 0 : k + 1; }
 
 // len2 of the edge {a, b}: d = vs[hi] - vs[lo], dx * dx + dy * dy + dz * dz, left to right, float32
 __device__ inline float edge_len2(const float* __restrict__ vs, int32_t a, int32_t b) {
@@ -426,63 +397,49 @@ __global__ void flip_apply(const uint8_t* __restrict__ win, const int32_t* __res
   tri[3 * f1 + 2] = q[2];
 }
 
-// ---- export -----------------------------------------------------------------------------------------------------------------
-__global__ void widen32(const int32_t* __restrict__ in, int64_t n, int64_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = in[i];
-}
-
 // ---- host -------------------------------------------------------------------------------------------------------------------
-inline unsigned long long* ctr_of(sg_remesh* s) { return (unsigned long long*)s->ctr.p; }
-
-int sort_bits(int64_t V) {                           // the keys are below V * V < 2^62
-  int bits = 1;
-  while (bits < 62 && (((uint64_t)V * (uint64_t)V) >> bits) != 0) ++bits;
-  return bits;
-}
-
 // keys, sort, heads, ranks, edge pass on the mesh as it stands; resets the counters first.  No host synchronisation unless a
 // scratch buffer has to grow.
 int analyse(sg_remesh* s, bool with_valence, hipStream_t stream) {
   const int64_t V = s->V, F = s->F, n = 3 * F;
-  for (Buf* b : {&s->keys_a, &s->keys_b, &s->cand})
-    if (int rc = reserve(b, (size_t)n * sizeof(uint64_t), false, stream)) return rc;
-  for (Buf* b : {&s->vals_a, &s->vals_b, &s->head, &s->incl, &s->he_rank})
-    if (int rc = reserve(b, (size_t)n * sizeof(int32_t), false, stream)) return rc;
-  for (Buf* b : {&s->flag_a, &s->scan_a})
-    if (int rc = reserve(b, (size_t)(n + 1) * sizeof(int32_t), false, stream)) return rc;
-  for (Buf* b : {&s->flag_f, &s->scan_f, &s->best, &s->fpos})
-    if (int rc = reserve(b, (size_t)(F + 1) * sizeof(int32_t), false, stream)) return rc;
-  if (int rc = reserve(&s->win, (size_t)n, false, stream)) return rc;
-  if (int rc = reserve(&s->slot, (size_t)V * sizeof(uint64_t), false, stream)) return rc;
-  if (int rc = reserve(&s->val, (size_t)V * sizeof(int32_t), false, stream)) return rc;
-  const int bits = sort_bits(V);
+  for (auto* b : {&s->keys_a, &s->keys_b})
+    if (int rc = b->reserve(n, false, stream)) return rc;
+  if (int rc = s->cand.reserve(n, false, stream)) return rc;
+  for (auto* b : {&s->vals_a, &s->vals_b, &s->head, &s->incl, &s->he_rank})
+    if (int rc = b->reserve(n, false, stream)) return rc;
+  for (auto* b : {&s->flag_a, &s->scan_a})
+    if (int rc = b->reserve(n + 1, false, stream)) return rc;
+  for (auto* b : {&s->flag_f, &s->scan_f, &s->best, &s->fpos})
+    if (int rc = b->reserve(F + 1, false, stream)) return rc;
+  if (int rc = s->win.reserve(n, false, stream)) return rc;
+  if (int rc = s->slot.reserve(V, false, stream)) return rc;
+  if (int rc = s->val.reserve(V, false, stream)) return rc;
+  const int bits = bits_for((uint64_t)V * (uint64_t)V, 62);    // the keys are below V * V < 2^62
+  const int32_t *head = s->head.p, *flag_a = s->flag_a.p, *flag_f = s->flag_f.p;   // hipCUB's iterator arguments keep their const
   size_t tb_sort = 0, tb_incl = 0, tb_a = 0, tb_f = 0;
-  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, (const uint64_t*)s->keys_a.p, (uint64_t*)s->keys_b.p,
-                                                (const int32_t*)s->vals_a.p, (int32_t*)s->vals_b.p, (int)n, 0, bits, stream));
-  SG_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb_incl, (const int32_t*)s->head.p, (int32_t*)s->incl.p, (int)n, stream));
-  SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_a, (const int32_t*)s->flag_a.p, (int32_t*)s->scan_a.p, (int)(n + 1), stream));
-  SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_f, (const int32_t*)s->flag_f.p, (int32_t*)s->scan_f.p, (int)(F + 1), stream));
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, s->keys_a.p, s->keys_b.p, s->vals_a.p, s->vals_b.p, (int)n, 0,
+                                                bits, stream));
+  SG_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb_incl, head, s->incl.p, (int)n, stream));
+  SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_a, flag_a, s->scan_a.p, (int)(n + 1), stream));
+  SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_f, flag_f, s->scan_f.p, (int)(F + 1), stream));
   size_t tb = tb_sort;
   for (size_t t : {tb_incl, tb_a, tb_f}) tb = t > tb ? t : tb;
-  if (int rc = reserve(&s->temp, tb ? tb : 16, false, stream)) return rc;
+  if (int rc = s->temp.reserve(tb ? tb : 16, false, stream)) return rc;
 
-  reset_counters<<<1, 64, 0, stream>>>(ctr_of(s));
+  reset_counters<<<1, 64, 0, stream>>>(s->ctr.p);
   SG_HIP_TRY(hipMemsetAsync(s->border.p, 0, (size_t)V, stream));
   if (with_valence) SG_HIP_TRY(hipMemsetAsync(s->val.p, 0, (size_t)V * sizeof(int32_t), stream));
-  half_edge_keys<<<blocks_for(n), kThreads, 0, stream>>>((const int32_t*)s->tri.p, n, V, (uint64_t*)s->keys_a.p, (int32_t*)s->vals_a.p);
+  half_edge_keys<<<blocks_for(n), kThreads, 0, stream>>>(s->tri.p, n, V, s->keys_a.p, s->vals_a.p);
   SG_HIP_TRY(hipGetLastError());
   size_t tb_use = s->temp.cap;
-  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(s->temp.p, tb_use, (const uint64_t*)s->keys_a.p, (uint64_t*)s->keys_b.p,
-                                                (const int32_t*)s->vals_a.p, (int32_t*)s->vals_b.p, (int)n, 0, bits, stream));
-  mark_heads<<<blocks_for(n), kThreads, 0, stream>>>((const uint64_t*)s->keys_b.p, n, (int32_t*)s->head.p);
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(s->temp.p, tb_use, s->keys_a.p, s->keys_b.p, s->vals_a.p, s->vals_b.p, (int)n, 0,
+                                                bits, stream));
+  mark_heads<<<blocks_for(n), kThreads, 0, stream>>>(s->keys_b.p, n, s->head.p);
   SG_HIP_TRY(hipGetLastError());
   tb_use = s->temp.cap;
-  SG_HIP_TRY(hipcub::DeviceScan::InclusiveSum(s->temp.p, tb_use, (const int32_t*)s->head.p, (int32_t*)s->incl.p, (int)n, stream));
-  edge_pass<<<blocks_for(n), kThreads, 0, stream>>>((const uint64_t*)s->keys_b.p, (const int32_t*)s->vals_b.p,
-                                                   (const int32_t*)s->head.p, (const int32_t*)s->incl.p, n, F, V,
-                                                   (const int32_t*)s->tri.p, (int32_t*)s->he_rank.p, (uint8_t*)s->border.p,
-                                                   with_valence ? (int32_t*)s->val.p : nullptr, ctr_of(s));
+  SG_HIP_TRY(hipcub::DeviceScan::InclusiveSum(s->temp.p, tb_use, head, s->incl.p, (int)n, stream));
+  edge_pass<<<blocks_for(n), kThreads, 0, stream>>>(s->keys_b.p, s->vals_b.p, s->head.p, s->incl.p, n, F, V, s->tri.p,
+                                                   s->he_rank.p, s->border.p, with_valence ? s->val.p : nullptr, s->ctr.p);
   SG_HIP_TRY(hipGetLastError());
   return SG_OK;
 }
@@ -495,23 +452,12 @@ int read_counters(sg_remesh* s, unsigned long long* h, hipStream_t stream) {
 
 }  // namespace
 
-void destroy_remesh(sg_remesh* s) {
-  if (!s) return;
-  for (Buf* b : {&s->vs, &s->par, &s->tri, &s->border, &s->keys_a, &s->keys_b, &s->vals_a, &s->vals_b, &s->head, &s->incl,
-                 &s->he_rank, &s->best, &s->fpos, &s->flag_a, &s->scan_a, &s->flag_f, &s->scan_f, &s->cand, &s->win, &s->slot,
-                 &s->val, &s->temp, &s->ctr})
-    if (b->p) (void)hipFree(b->p);
-  delete s;
-}
+void destroy_remesh(sg_remesh* s) { delete s; }
 
 int remesh_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, hipStream_t stream, sg_remesh** out) {
   SG_REQUIRE(V < ((int64_t)1 << 31) && 3 * F < ((int64_t)1 << 31), "sg_remesh_create: sizes must fit int32");
-  sg_remesh* s = new (std::nothrow) sg_remesh;
+  std::unique_ptr<sg_remesh> s(new (std::nothrow) sg_remesh);
   SG_REQUIRE(s != nullptr, "sg_remesh_create: out of host memory");
-  struct Guard {
-    sg_remesh* s;
-    ~Guard() { destroy_remesh(s); }
-  } guard{s};
   s->V = s->V0 = V;
   s->F = s->F0 = F;
   s->h_ctr[kBadFace] = s->h_ctr[kBadVertex] = s->h_ctr[kBadKey] = ~0ull;
@@ -519,32 +465,30 @@ int remesh_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, h
   if (V == 0) {
     SG_REQUIRE(F == 0, "sg_remesh_create: face refers to a vertex outside [0, 0)");
     s->valid = true;
-    guard.s = nullptr;
-    *out = s;
+    *out = s.release();
     return SG_OK;
   }
-  if (int rc = reserve(&s->ctr, kCounters * sizeof(unsigned long long), false, stream)) return rc;
-  if (int rc = reserve(&s->vs, (size_t)V * 3 * sizeof(float), false, stream)) return rc;
-  if (int rc = reserve(&s->par, (size_t)V * 2 * sizeof(int32_t), false, stream)) return rc;
-  if (int rc = reserve(&s->border, (size_t)V, false, stream)) return rc;
-  if (int rc = reserve(&s->tri, (size_t)F * 3 * sizeof(int32_t), false, stream)) return rc;
+  if (int rc = s->ctr.reserve(kCounters, false, stream)) return rc;
+  if (int rc = s->vs.reserve(3 * V, false, stream)) return rc;
+  if (int rc = s->par.reserve(2 * V, false, stream)) return rc;
+  if (int rc = s->border.reserve(V, false, stream)) return rc;
+  if (int rc = s->tri.reserve(3 * F, false, stream)) return rc;
   SG_HIP_TRY(hipMemcpyAsync(s->vs.p, vs, (size_t)V * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
   SG_HIP_TRY(hipMemsetAsync(s->border.p, 0, (size_t)V, stream));
-  reset_counters<<<1, 64, 0, stream>>>(ctr_of(s));
-  if (F > 0) classify_faces<<<blocks_for(F), kThreads, 0, stream>>>(faces, F, V, (int32_t*)s->tri.p, ctr_of(s));
-  check_vertices<<<blocks_for(V), kThreads, 0, stream>>>((const float*)s->vs.p, V, (int32_t*)s->par.p, ctr_of(s));
+  reset_counters<<<1, 64, 0, stream>>>(s->ctr.p);
+  if (F > 0) classify_faces<<<blocks_for(F), kThreads, 0, stream>>>(faces, F, V, s->tri.p, s->ctr.p);
+  check_vertices<<<blocks_for(V), kThreads, 0, stream>>>(s->vs.p, V, s->par.p, s->ctr.p);
   SG_HIP_TRY(hipGetLastError());
   unsigned long long first[kCounters];
-  if (int rc = read_counters(s, first, stream)) return rc;
+  if (int rc = read_counters(s.get(), first, stream)) return rc;
   SG_REQUIRE(!first[kOutOfRange], "sg_remesh_create: face refers to a vertex outside [0, %lld)", (long long)V);
   if (F > 0) {
-    if (int rc = analyse(s, false, stream)) return rc;   // resets the counters: the face and vertex counts are kept in `first`
-    if (int rc = read_counters(s, s->h_ctr, stream)) return rc;
+    if (int rc = analyse(s.get(), false, stream)) return rc;   // resets the counters: the face and vertex counts are kept in `first`
+    if (int rc = read_counters(s.get(), s->h_ctr, stream)) return rc;
   }
   for (int i : {(int)kDegenerate, (int)kBadFace, (int)kNonFinite, (int)kBadVertex}) s->h_ctr[i] = first[i];
   s->valid = !s->h_ctr[kDegenerate] && !s->h_ctr[kNonFinite] && !s->h_ctr[kNonManifold] && !s->h_ctr[kMisoriented];
-  guard.s = nullptr;
-  *out = s;
+  *out = s.release();
   return SG_OK;
 }
 
@@ -578,20 +522,17 @@ int remesh_split(sg_remesh* s, float thr2, int64_t max_rounds, hipStream_t strea
   for (int64_t round = 0;; ++round) {
     const int64_t V = s->V, F = s->F, n = 3 * F;
     if (int rc = analyse(s, false, stream)) return rc;
-    face_best_edge<<<blocks_for(F), kThreads, 0, stream>>>((const int32_t*)s->tri.p, (const int32_t*)s->he_rank.p,
-                                                          (const float*)s->vs.p, F, thr2, (int32_t*)s->best.p);
+    face_best_edge<<<blocks_for(F), kThreads, 0, stream>>>(s->tri.p, s->he_rank.p, s->vs.p, F, thr2, s->best.p);
     SG_HIP_TRY(hipMemsetAsync(s->flag_f.p, 0, (size_t)(F + 1) * sizeof(int32_t), stream));
-    select_split<<<blocks_for(n + 1), kThreads, 0, stream>>>((const int32_t*)s->vals_b.p, (const int32_t*)s->head.p,
-                                                            (const int32_t*)s->incl.p, n, F, (const int32_t*)s->tri.p,
-                                                            (const float*)s->vs.p, thr2, (const int32_t*)s->best.p,
-                                                            (int32_t*)s->flag_a.p, (int32_t*)s->flag_f.p, (int32_t*)s->fpos.p,
-                                                            ctr_of(s));
+    select_split<<<blocks_for(n + 1), kThreads, 0, stream>>>(s->vals_b.p, s->head.p, s->incl.p, n, F, s->tri.p, s->vs.p, thr2,
+                                                            s->best.p, s->flag_a.p, s->flag_f.p, s->fpos.p, s->ctr.p);
     SG_HIP_TRY(hipGetLastError());
+    const int32_t *flag_a = s->flag_a.p, *flag_f = s->flag_f.p;   // hipCUB's iterator arguments keep their const
     size_t tb = s->temp.cap;
-    SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->temp.p, tb, (const int32_t*)s->flag_a.p, (int32_t*)s->scan_a.p, (int)(n + 1), stream));
+    SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->temp.p, tb, flag_a, s->scan_a.p, (int)(n + 1), stream));
     tb = s->temp.cap;
-    SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->temp.p, tb, (const int32_t*)s->flag_f.p, (int32_t*)s->scan_f.p, (int)(F + 1), stream));
-    store_totals<<<1, 1, 0, stream>>>((const int32_t*)s->scan_a.p, n, (const int32_t*)s->scan_f.p, F, ctr_of(s));
+    SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->temp.p, tb, flag_f, s->scan_f.p, (int)(F + 1), stream));
+    store_totals<<<1, 1, 0, stream>>>(s->scan_a.p, n, s->scan_f.p, F, s->ctr.p);
     SG_HIP_TRY(hipGetLastError());
     unsigned long long c[kCounters];
     if (int rc = read_counters(s, c, stream)) return rc;       // the round's one synchronisation: count -> emit
@@ -601,18 +542,14 @@ int remesh_split(sg_remesh* s, float thr2, int64_t max_rounds, hipStream_t strea
                (long long)S, (long long)T);
     if (S == 0 || round >= max_rounds) break;
     SG_REQUIRE(V + S < ((int64_t)1 << 31) && 3 * (F + T) < ((int64_t)1 << 31), "sg_remesh_split: sizes must fit int32");
-    if (int rc = reserve(&s->vs, (size_t)(V + S) * 3 * sizeof(float), true, stream)) return rc;
-    if (int rc = reserve(&s->par, (size_t)(V + S) * 2 * sizeof(int32_t), true, stream)) return rc;
-    if (int rc = reserve(&s->border, (size_t)(V + S), true, stream)) return rc;
-    if (int rc = reserve(&s->tri, (size_t)(F + T) * 3 * sizeof(int32_t), true, stream)) return rc;
-    emit_split_vertices<<<blocks_for(n), kThreads, 0, stream>>>((const int32_t*)s->vals_b.p, (const int32_t*)s->head.p,
-                                                               (const int32_t*)s->flag_a.p, (const int32_t*)s->scan_a.p, n, V, S,
-                                                               (const int32_t*)s->tri.p, (float*)s->vs.p, (int32_t*)s->par.p,
-                                                               (uint8_t*)s->border.p);
-    emit_split_faces<<<blocks_for(F), kThreads, 0, stream>>>((const int32_t*)s->flag_f.p, (const int32_t*)s->scan_f.p,
-                                                            (const int32_t*)s->fpos.p, (const int32_t*)s->scan_a.p,
-                                                            (const int32_t*)s->he_rank.p, (const int32_t*)s->best.p, F, V, S, T, n,
-                                                            (int32_t*)s->tri.p);
+    if (int rc = s->vs.reserve(3 * (V + S), true, stream)) return rc;
+    if (int rc = s->par.reserve(2 * (V + S), true, stream)) return rc;
+    if (int rc = s->border.reserve(V + S, true, stream)) return rc;
+    if (int rc = s->tri.reserve(3 * (F + T), true, stream)) return rc;
+    emit_split_vertices<<<blocks_for(n), kThreads, 0, stream>>>(s->vals_b.p, s->head.p, s->flag_a.p, s->scan_a.p, n, V, S,
+                                                               s->tri.p, s->vs.p, s->par.p, s->border.p);
+    emit_split_faces<<<blocks_for(F), kThreads, 0, stream>>>(s->flag_f.p, s->scan_f.p, s->fpos.p, s->scan_a.p, s->he_rank.p,
+                                                            s->best.p, F, V, S, T, n, s->tri.p);
     SG_HIP_TRY(hipGetLastError());
     s->V = V + S;
     s->F = F + T;
@@ -631,15 +568,10 @@ int remesh_flip(sg_remesh* s, int64_t max_rounds, hipStream_t stream, int64_t* c
   for (int64_t round = 0;; ++round) {
     if (int rc = analyse(s, true, stream)) return rc;
     SG_HIP_TRY(hipMemsetAsync(s->slot.p, 0, (size_t)V * sizeof(uint64_t), stream));
-    valence_deviation<<<blocks_for(V), kThreads, 0, stream>>>((const int32_t*)s->val.p, (const uint8_t*)s->border.p, V, ctr_of(s));
-    flip_candidates<<<blocks_for(n), kThreads, 0, stream>>>((const uint64_t*)s->keys_b.p, (const int32_t*)s->vals_b.p,
-                                                           (const int32_t*)s->head.p, (const int32_t*)s->incl.p, n, V,
-                                                           (const int32_t*)s->tri.p, (const float*)s->vs.p, (const int32_t*)s->val.p,
-                                                           (const uint8_t*)s->border.p, (unsigned long long*)s->cand.p,
-                                                           (unsigned long long*)s->slot.p);
-    flip_check<<<blocks_for(n), kThreads, 0, stream>>>((const unsigned long long*)s->cand.p, (const int32_t*)s->vals_b.p,
-                                                      (const int32_t*)s->tri.p, (const unsigned long long*)s->slot.p, n,
-                                                      (uint8_t*)s->win.p, ctr_of(s));
+    valence_deviation<<<blocks_for(V), kThreads, 0, stream>>>(s->val.p, s->border.p, V, s->ctr.p);
+    flip_candidates<<<blocks_for(n), kThreads, 0, stream>>>(s->keys_b.p, s->vals_b.p, s->head.p, s->incl.p, n, V, s->tri.p,
+                                                           s->vs.p, s->val.p, s->border.p, s->cand.p, s->slot.p);
+    flip_check<<<blocks_for(n), kThreads, 0, stream>>>(s->cand.p, s->vals_b.p, s->tri.p, s->slot.p, n, s->win.p, s->ctr.p);
     SG_HIP_TRY(hipGetLastError());
     unsigned long long c[kCounters];
     if (int rc = read_counters(s, c, stream)) return rc;       // the round's one synchronisation: count -> apply
@@ -648,7 +580,7 @@ int remesh_flip(sg_remesh* s, int64_t max_rounds, hipStream_t stream, int64_t* c
     deviation[1] = (int64_t)c[kDeviation];
     SG_REQUIRE(W >= 0 && W <= n, "sg_remesh_flip: winner count %lld out of range", (long long)W);
     if (W == 0 || round >= max_rounds) break;
-    flip_apply<<<blocks_for(n), kThreads, 0, stream>>>((const uint8_t*)s->win.p, (const int32_t*)s->vals_b.p, n, (int32_t*)s->tri.p);
+    flip_apply<<<blocks_for(n), kThreads, 0, stream>>>(s->win.p, s->vals_b.p, n, s->tri.p);
     SG_HIP_TRY(hipGetLastError());
     counts[round] = W;
     *n_rounds = round + 1;
@@ -662,10 +594,10 @@ int remesh_export(const sg_remesh* s, float* vs, int64_t* faces, int64_t* parent
   if (V == 0 && F == 0) return SG_OK;               // nothing to write, no device to ask
   if (V > 0) {
     SG_HIP_TRY(hipMemcpyAsync(vs, s->vs.p, (size_t)V * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    widen32<<<blocks_for(2 * V), kThreads, 0, stream>>>((const int32_t*)s->par.p, 2 * V, parents);
+    widen32<<<blocks_for(2 * V), kThreads, 0, stream>>>(s->par.p, 2 * V, parents);
     if (border) SG_HIP_TRY(hipMemcpyAsync(border, s->border.p, (size_t)V, hipMemcpyDeviceToDevice, stream));
   }
-  if (F > 0) widen32<<<blocks_for(3 * F), kThreads, 0, stream>>>((const int32_t*)s->tri.p, 3 * F, faces);
+  if (F > 0) widen32<<<blocks_for(3 * F), kThreads, 0, stream>>>(s->tri.p, 3 * F, faces);
   SG_HIP_TRY(hipGetLastError());
   return SG_OK;
 }

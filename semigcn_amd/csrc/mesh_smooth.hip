@@ -15,33 +15,24 @@
 // so that one neighbour is one 16-byte load and the divisor rides along with the vertex's own position.
 // Bytes per step and vertex at valence d: 16 d (gathers) + 16 (own) + 16 (store) + 4 d (ids) + d (weights) + 8 (row bounds);
 // d = 6: 166 B, of which the 32 MB of positions of a 1 M mesh stay in the last-level cache from step to step.
-#include <hipcub/hipcub.hpp>
-
+#include <memory>
 #include <new>
 
-#include "sg_common.h"
+#include "mesh_common.h"
 
 struct sg_smooth {
   int64_t V = 0, nnz = 0;
-  int32_t* rowptr = nullptr;   // [V + 1]
-  int32_t* idx = nullptr;      // [nnz] neighbour ids, ascending inside a row
-  uint8_t* w = nullptr;        // [nnz] w_ij (0: an interior edge of a border vertex)
-  float* den = nullptr;        // [V] 1 + sum_j w_ij, 0 for a vertex without weighted edges
-  float4* buf[2] = {nullptr, nullptr};   // [V] each: the ping-pong positions of sg_smooth_run
+  sg::DeviceBuf<int32_t> rowptr;   // [V + 1]
+  sg::DeviceBuf<int32_t> idx;      // [nnz] neighbour ids, ascending inside a row
+  sg::DeviceBuf<uint8_t> w;        // [nnz] w_ij (0: an interior edge of a border vertex)
+  sg::DeviceBuf<float> den;        // [V] 1 + sum_j w_ij, 0 for a vertex without weighted edges
+  sg::DeviceBuf<float4> buf[2];    // [V] each: the ping-pong positions of sg_smooth_run
 };
 
 namespace sg {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kRedBlocks = 1024;
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-struct DeviceBuf {
-  void* p = nullptr;
-  ~DeviceBuf() { if (p) (void)hipFree(p); }
-};
 
 // ---- mean edge length ------------------------------------------------------------------------------------------------
 // float32 lengths, float64 sums: per thread over a grid-stride walk, then over the block, in a fixed order.  An edge that
@@ -89,7 +80,7 @@ __global__ void directed_keys(const int64_t* __restrict__ faces, int64_t n_half,
   if (h >= n_half) return;
   const int64_t f = h / 3;
   const int i = (int)(h - 3 * f);
-  const int64_t a = faces[3 * f + i], b = faces[3 * f + (i == 2 ? 0 : i + 1)];
+  const int64_t a = faces[3 * f + i], b = faces[3 * f + next3(i)];
   uint64_t k0 = ~0ull, k1 = ~0ull;
   if (a < 0 || a >= V || b < 0 || b >= V) {
     flags[0] = 1;
@@ -215,57 +206,43 @@ int launch_mean_edge_length(const float* vs, int64_t V, const int64_t* edges, in
   return SG_OK;
 }
 
-void destroy_smooth(sg_smooth* s) {
-  if (!s) return;
-  if (s->rowptr) (void)hipFree(s->rowptr);
-  if (s->idx) (void)hipFree(s->idx);
-  if (s->w) (void)hipFree(s->w);
-  if (s->den) (void)hipFree(s->den);
-  if (s->buf[0]) (void)hipFree(s->buf[0]);
-  if (s->buf[1]) (void)hipFree(s->buf[1]);
-  delete s;
-}
+void destroy_smooth(sg_smooth* s) { delete s; }
 
 int smooth_create(const int64_t* faces, int64_t F, int64_t V, hipStream_t stream, sg_smooth** out) {
   const int64_t n_half = 3 * F, n_dir = 6 * F;
   SG_REQUIRE(V < ((int64_t)1 << 31) && n_dir < ((int64_t)1 << 31), "sg_smooth_create: sizes must fit int32");
-  sg_smooth* s = new (std::nothrow) sg_smooth;
+  std::unique_ptr<sg_smooth> s(new (std::nothrow) sg_smooth);
   SG_REQUIRE(s != nullptr, "sg_smooth_create: out of host memory");
-  struct Guard {
-    sg_smooth* s;
-    ~Guard() { destroy_smooth(s); }
-  } guard{s};
   s->V = V;
-  SG_HIP_TRY(hipMalloc(&s->rowptr, (size_t)(V + 1) * sizeof(int32_t)));
-  SG_HIP_TRY(hipMalloc(&s->den, (size_t)(V > 0 ? V : 1) * sizeof(float)));
-  SG_HIP_TRY(hipMalloc(&s->buf[0], (size_t)(V > 0 ? V : 1) * sizeof(float4)));
-  SG_HIP_TRY(hipMalloc(&s->buf[1], (size_t)(V > 0 ? V : 1) * sizeof(float4)));
+  SG_HIP_TRY(s->rowptr.alloc(V + 1));
+  SG_HIP_TRY(s->den.alloc(V));
+  SG_HIP_TRY(s->buf[0].alloc(V));
+  SG_HIP_TRY(s->buf[1].alloc(V));
 
-  DeviceBuf keys_a, keys_b, ukeys, counts, n_runs, flags, temp;
+  DeviceBuf<uint64_t> keys_a, keys_b, ukeys;
+  DeviceBuf<int32_t> counts;
+  DeviceBuf<int> n_runs, flags;
+  DeviceBuf<char> temp;
   int h_runs = 0, h_flags[3] = {0, 0, 0};
-  SG_HIP_TRY(hipMalloc(&flags.p, 3 * sizeof(int)));
+  SG_HIP_TRY(flags.alloc(3));
   SG_HIP_TRY(hipMemsetAsync(flags.p, 0, 3 * sizeof(int), stream));
   if (F > 0) {
-    SG_HIP_TRY(hipMalloc(&keys_a.p, (size_t)n_dir * sizeof(uint64_t)));
-    SG_HIP_TRY(hipMalloc(&keys_b.p, (size_t)n_dir * sizeof(uint64_t)));
-    SG_HIP_TRY(hipMalloc(&ukeys.p, (size_t)n_dir * sizeof(uint64_t)));
-    SG_HIP_TRY(hipMalloc(&counts.p, (size_t)n_dir * sizeof(int32_t)));
-    SG_HIP_TRY(hipMalloc(&n_runs.p, sizeof(int)));
-    directed_keys<<<blocks_for(n_half), kThreads, 0, stream>>>(faces, n_half, V, (uint64_t*)keys_a.p, (int*)flags.p);
+    SG_HIP_TRY(keys_a.alloc(n_dir));
+    SG_HIP_TRY(keys_b.alloc(n_dir));
+    SG_HIP_TRY(ukeys.alloc(n_dir));
+    SG_HIP_TRY(counts.alloc(n_dir));
+    SG_HIP_TRY(n_runs.alloc(1));
+    directed_keys<<<blocks_for(n_half), kThreads, 0, stream>>>(faces, n_half, V, keys_a.p, flags.p);
     SG_HIP_TRY(hipGetLastError());
-    int hi_bits = 1;
-    while (hi_bits < 32 && ((uint64_t)V >> hi_bits) != 0) ++hi_bits;
+    const int hi_bits = bits_for((uint64_t)V, 32);
+    const uint64_t* sorted = keys_b.p;      // hipCUB's iterator argument keeps the const it had
     size_t t1 = 0, t2 = 0;
-    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p, (int)n_dir, 0,
-                                                 32 + hi_bits, stream));
-    SG_HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, (const uint64_t*)keys_b.p, (uint64_t*)ukeys.p,
-                                                     (int32_t*)counts.p, (int*)n_runs.p, (int)n_dir, stream));
+    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, keys_a.p, keys_b.p, (int)n_dir, 0, 32 + hi_bits, stream));
+    SG_HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, sorted, ukeys.p, counts.p, n_runs.p, (int)n_dir, stream));
     const size_t tb = t1 > t2 ? t1 : t2;
-    SG_HIP_TRY(hipMalloc(&temp.p, tb ? tb : 16));
-    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp.p, t1, (const uint64_t*)keys_a.p, (uint64_t*)keys_b.p, (int)n_dir, 0,
-                                                 32 + hi_bits, stream));
-    SG_HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(temp.p, t2, (const uint64_t*)keys_b.p, (uint64_t*)ukeys.p,
-                                                     (int32_t*)counts.p, (int*)n_runs.p, (int)n_dir, stream));
+    SG_HIP_TRY(temp.alloc(tb ? tb : 16));
+    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp.p, t1, keys_a.p, keys_b.p, (int)n_dir, 0, 32 + hi_bits, stream));
+    SG_HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(temp.p, t2, sorted, ukeys.p, counts.p, n_runs.p, (int)n_dir, stream));
     SG_HIP_TRY(hipMemcpyAsync(&h_runs, n_runs.p, sizeof(int), hipMemcpyDeviceToHost, stream));
     SG_HIP_TRY(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, stream));
     SG_HIP_TRY(hipStreamSynchronize(stream));
@@ -274,20 +251,18 @@ int smooth_create(const int64_t* faces, int64_t F, int64_t V, hipStream_t stream
     SG_REQUIRE(h_runs >= 0 && h_runs <= n_dir, "sg_smooth_create: run count %d out of range", h_runs);
   }
   s->nnz = h_runs;
-  SG_HIP_TRY(hipMalloc(&s->idx, (size_t)(h_runs > 0 ? h_runs : 1) * sizeof(int32_t)));
-  SG_HIP_TRY(hipMalloc(&s->w, (size_t)(h_runs > 0 ? h_runs : 1)));
-  row_starts<<<blocks_for(V + 1), kThreads, 0, stream>>>((const uint64_t*)ukeys.p, h_runs, V, s->rowptr);
+  SG_HIP_TRY(s->idx.alloc(h_runs));
+  SG_HIP_TRY(s->w.alloc(h_runs));
+  row_starts<<<blocks_for(V + 1), kThreads, 0, stream>>>(ukeys.p, h_runs, V, s->rowptr.p);
   SG_HIP_TRY(hipGetLastError());
   if (V > 0) {
-    row_weights<<<blocks_for(V), kThreads, 0, stream>>>((const uint64_t*)ukeys.p, (const int32_t*)counts.p, s->rowptr, V, s->idx,
-                                                       s->w, s->den, (int*)flags.p);
+    row_weights<<<blocks_for(V), kThreads, 0, stream>>>(ukeys.p, counts.p, s->rowptr.p, V, s->idx.p, s->w.p, s->den.p, flags.p);
     SG_HIP_TRY(hipGetLastError());
   }
   SG_HIP_TRY(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, stream));
   SG_HIP_TRY(hipStreamSynchronize(stream));   // the temporaries are freed on return
   SG_REQUIRE(!h_flags[2], "sg_smooth_create: an edge with more than 255 faces");
-  guard.s = nullptr;
-  *out = s;
+  *out = s.release();
   return SG_OK;
 }
 
@@ -299,14 +274,14 @@ int smooth_run(sg_smooth* s, const float* in, float* out, const uint8_t* movable
     return SG_OK;
   }
   const unsigned grid = blocks_for(V);
-  smooth_pack<<<grid, kThreads, 0, stream>>>(in, s->den, movable, V, s->buf[0]);
+  smooth_pack<<<grid, kThreads, 0, stream>>>(in, s->den.p, movable, V, s->buf[0].p);
   SG_HIP_TRY(hipGetLastError());
-  float4 *a = s->buf[0], *b = s->buf[1];
+  float4 *a = s->buf[0].p, *b = s->buf[1].p;
   for (int r = 0; r + 1 < steps; ++r) {
-    smooth_step<false><<<grid, kThreads, 0, stream>>>(s->rowptr, s->idx, s->w, a, V, b, nullptr);
+    smooth_step<false><<<grid, kThreads, 0, stream>>>(s->rowptr.p, s->idx.p, s->w.p, a, V, b, nullptr);
     float4* t = a; a = b; b = t;
   }
-  smooth_step<true><<<grid, kThreads, 0, stream>>>(s->rowptr, s->idx, s->w, a, V, nullptr, out);
+  smooth_step<true><<<grid, kThreads, 0, stream>>>(s->rowptr.p, s->idx.p, s->w.p, a, V, nullptr, out);
   SG_HIP_TRY(hipGetLastError());
   return SG_OK;
 }

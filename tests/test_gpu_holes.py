@@ -239,6 +239,32 @@ def test_max_hole_edges():
     assert HO.half_edge_stats(both.faces.cpu().numpy()) == (1, 0) and HO.euler_characteristic(both.faces.cpu().numpy()) == 2
 
 
+def test_plan_again_on_the_same_plan():
+    """``plan`` drops the sizes of the call before it: uncapped, capped at 20, uncapped again on ONE FillPlan, each emit against
+    the oracle result test_max_hole_edges asserts (faces and ``filled`` exactly, positions within its 1e-5 x diagonal)."""
+    from semigcn_amd import capi
+    vs, faces, uncapped = case("planar")
+    V = vs.shape[0]
+    d_vs = dev(vs)
+    plan = capi.FillPlan(dev(faces), V)
+    try:
+        plan.plan(None)
+        for cap, want in ((20, HO.fill_holes(vs, faces, max_hole_edges=20)), (None, uncapped)):
+            w_vs, w_faces, _, w_filled, _ = want
+            Vn, Fn = plan.plan(cap)
+            assert (Vn, Fn) == (w_vs.shape[0] - V, w_faces.shape[0] - faces.shape[0])
+            new_vs = torch.empty((Vn, 3), dtype=torch.float32, device=DEV)
+            new_faces = torch.empty((Fn, 3), dtype=torch.int64, device=DEV)
+            filled = plan.emit(d_vs, new_vs, new_faces)
+            assert np.array_equal(new_faces.cpu().numpy(), w_faces[faces.shape[0]:])
+            assert np.array_equal(filled.cpu().numpy(), w_filled)
+            assert np.abs(new_vs.cpu().numpy().astype(np.float64) - w_vs[V:]).max() <= 1e-5 * diagonal(vs)
+        assert w_filled.all() and Vn > 12 // 2 + 1                  # the last round filled the border loop as well
+    finally:
+        torch.cuda.current_stream().synchronize()                   # the plan's buffers are freed with it
+        plan.close()
+
+
 # ---- fairing -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("steps", [1, 30])
 def test_fairing_is_the_existing_smoothing(steps):
