@@ -337,7 +337,16 @@ SG_API int sg_face_mask(const int64_t* faces, int64_t F, int64_t V, const uint64
  *   that point lies on: the one with the smallest float32 distance, the lowest
  *   index on an exact tie; closest_or_null [N,3] = that point.  signed_dist != 0:
  *   dist takes the sign of dot((b-a) x (c-a), p - closest) of that face, a zero
- *   distance is +0.  Asynchronous; bit-reproducible (no atomics).
+ *   distance is +0.  A point with a NaN or an infinite coordinate has no
+ *   closest point: its row is dist = +inf (signed or not), face = 0x7fffffff,
+ *   closest = (nan, nan, nan), and the other rows are not affected; test
+ *   isinf(dist) before indexing with face.  The normal, the barycentrics and
+ *   the plane offset of a triangle are float64 on the float32 local frame:
+ *   |dist - exact| <= 1e-5 (dist + longest edge) holds for needles down to the
+ *   zero-area threshold (sine of the angle at the first vertex 1e-5) and below
+ *   it, where the closest point is taken on the face's three edges (a face of
+ *   exactly zero area has no normal: sign +).  Asynchronous; bit-reproducible
+ *   (no atomics).
  * sg_mesh_distance_reduce: one pass over the N vertices gt_vs [N,3] of gt with
  *   q [N] (signed distances gt -> out): out (device, 4 doubles) =
  *   (sum |q|, sum over the hole of |q|, hole count, diagonal of gt's vertex box).

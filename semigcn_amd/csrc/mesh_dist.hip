@@ -14,7 +14,8 @@
 // and the tree only.  Bound: latency of the dependent node / triangle loads, not HBM bandwidth.
 //
 // Point-triangle arithmetic runs in the triangle's local frame (p - a, b - a, c - a): the rounding
-// error then scales with the distance and the triangle size, not with the coordinates.
+// error then scales with the distance and the triangle size, not with the coordinates.  What rests
+// on the normal is float64 (tri_offset), so the error does not grow with the triangle's thinness.
 #include <memory>
 #include <new>
 
@@ -229,9 +230,6 @@ __global__ void point_keys(const float* __restrict__ pts, int64_t N, const float
 
 __device__ __forceinline__ float3 sub3(float3 a, float3 b) { return make_float3(a.x - b.x, a.y - b.y, a.z - b.z); }
 __device__ __forceinline__ float dot3(float3 a, float3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ float3 cross3(float3 a, float3 b) {
-  return make_float3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
-}
 
 // q - (closest point of the segment s0 + t d, t in [0, 1]); a zero-length segment is its point.
 __device__ __forceinline__ float3 seg_offset(float3 q, float3 s0, float3 d) {
@@ -242,12 +240,18 @@ __device__ __forceinline__ float3 seg_offset(float3 q, float3 s0, float3 d) {
   return make_float3(w.x - t * d.x, w.y - t * d.y, w.z - t * d.z);
 }
 
-// Offset r = p - closest point of the triangle (0, e1, e2), p in the local frame; *side = dot(e1 x e2, r).
+// Offset r = p - closest point of the triangle (0, e1, e2), p in the local frame; *below = dot(e1 x e2, r) < 0.
 // Inside the triangle's prism the closest point is p's projection onto the plane; elsewhere (and for a zero-area
 // triangle: collinear or repeated vertices) it lies on one of the three edges.
-__device__ __forceinline__ float3 tri_offset(float3 p, float3 e1, float3 e2, float* side) {
-  const float3 n = cross3(e1, e2);
-  const float nn = dot3(n, n);
+//
+// The normal and everything derived from it (the barycentrics, the plane offset, the side) are float64 on the float32
+// p, e1, e2.  A product of two float32 is exact in float64, so n = e1 x e2 keeps a relative error of 2^-52 / sin(angle
+// of e1, e2); in float32 it is 2^-23 / sin, and the plane distance of a point over the far end of a needle of length l
+// was off by 1e-7 l / sin: beyond 1e-5 l from sin = 1e-3 down.  The edge offsets do not involve n and stay float32.
+__device__ __forceinline__ float3 tri_offset(float3 p, float3 e1, float3 e2, bool* below) {
+  const double px = p.x, py = p.y, pz = p.z, ax = e1.x, ay = e1.y, az = e1.z, bx = e2.x, by = e2.y, bz = e2.z;
+  const double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+  const double nn = nx * nx + ny * ny + nz * nz;
   const float3 zero = make_float3(0.f, 0.f, 0.f);
   float3 r = seg_offset(p, zero, e1);
   float best = dot3(r, r);
@@ -259,15 +263,17 @@ __device__ __forceinline__ float3 tri_offset(float3 p, float3 e1, float3 e2, flo
   if (d3 < best) { r = r3; best = d3; }
   // a sliver whose normal is below rounding (sin of its angle < 1e-5) counts as degenerate: its edges are then within
   // 5e-6 of its size of every point of it
-  if (nn > 1e-10f * dot3(e1, e1) * dot3(e2, e2)) {
-    const float b1 = dot3(cross3(p, e2), n) / nn, b2 = dot3(cross3(e1, p), n) / nn;
-    if (b1 >= 0.f && b2 >= 0.f && b1 + b2 <= 1.f) {
-      const float h = dot3(p, n) / nn;
-      const float3 rp = make_float3(h * n.x, h * n.y, h * n.z);
+  if (nn > 1e-10 * (ax * ax + ay * ay + az * az) * (bx * bx + by * by + bz * bz)) {
+    // the barycentrics times nn: dot(p x e2, n) and dot(e1 x p, n)
+    const double b1 = (py * bz - pz * by) * nx + (pz * bx - px * bz) * ny + (px * by - py * bx) * nz;
+    const double b2 = (ay * pz - az * py) * nx + (az * px - ax * pz) * ny + (ax * py - ay * px) * nz;
+    if (b1 >= 0.0 && b2 >= 0.0 && b1 + b2 <= nn) {
+      const double h = (px * nx + py * ny + pz * nz) / nn;
+      const float3 rp = make_float3((float)(h * nx), (float)(h * ny), (float)(h * nz));
       if (dot3(rp, rp) <= best) r = rp;
     }
   }
-  *side = dot3(n, r);
+  *below = nx * r.x + ny * r.y + nz * r.z < 0.0;
   return r;
 }
 
@@ -281,7 +287,7 @@ __device__ __forceinline__ float box_dist(float4 lo, float4 hi, float3 p) {
 struct Best {
   float d = INFINITY;
   int face = 0x7fffffff;
-  float side = 0.f;
+  bool below = false;   // the point is on the negative side of the face's normal
   float3 c = make_float3(0.f, 0.f, 0.f);
 };
 
@@ -291,14 +297,14 @@ __device__ __forceinline__ void test_leaf(const float4* __restrict__ tri, int64_
   for (int64_t k = k0; k < k1; ++k) {
     const float4 a = tri[3 * k], e1 = tri[3 * k + 1], e2 = tri[3 * k + 2];
     const float3 q = make_float3(p.x - a.x, p.y - a.y, p.z - a.z);
-    float side;
-    const float3 r = tri_offset(q, make_float3(e1.x, e1.y, e1.z), make_float3(e2.x, e2.y, e2.z), &side);
+    bool below;
+    const float3 r = tri_offset(q, make_float3(e1.x, e1.y, e1.z), make_float3(e2.x, e2.y, e2.z), &below);
     const float d = sqrtf(dot3(r, r));
     const int f = __float_as_int(a.w);
     if (d < best.d || (d == best.d && f < best.face)) {     // ties: the lowest face index
       best.d = d;
       best.face = f;
-      best.side = side;
+      best.below = below;
       best.c = make_float3(p.x - r.x, p.y - r.y, p.z - r.z);
     }
   }
@@ -316,6 +322,12 @@ __global__ __launch_bounds__(kQueryThreads) void surface_query(const float4* __r
   if (t >= N) return;
   const int64_t i = (int64_t)(order[t] & 0xffffffffull);
   const float3 p = make_float3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
+  if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) {   // no distance to compare: (inf, no face, nan), and no walk
+    dist[i] = INFINITY;
+    face[i] = 0x7fffffff;
+    if (closest) closest[3 * i] = closest[3 * i + 1] = closest[3 * i + 2] = __int_as_float(0x7fc00000);
+    return;
+  }
   Best best;
   int cur = 0, sp = 0;
   while (true) {
@@ -341,7 +353,7 @@ __global__ __launch_bounds__(kQueryThreads) void surface_query(const float4* __r
     }
   }
   float d = best.d;
-  if (signed_dist && best.side < 0.f && d > 0.f) d = -d;     // sign of dot(n, p - closest); a zero distance is +0
+  if (signed_dist && best.below && d > 0.f) d = -d;     // sign of dot(n, p - closest); a zero distance is +0
   dist[i] = d;
   face[i] = best.face;
   if (closest) {

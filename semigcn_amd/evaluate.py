@@ -87,7 +87,9 @@ class Surface:
 
     def query(self, points, signed: bool = True):
         """(dist float32 [N], face int32 [N], closest float32 [N, 3]): the distance from every point to the surface
-        (signed by the face normal when ``signed``), the face the closest point lies on, and that point."""
+        (signed by the face normal when ``signed``), the face the closest point lies on, and that point.  A point with a
+        NaN or an infinite coordinate gets ``dist = inf``, ``face = 0x7fffffff`` and a NaN ``closest`` row, and leaves
+        the other rows alone: test ``torch.isinf(dist)`` before indexing with ``face``."""
         pts = _points(points)
         if pts.device != self.device:
             pts = pts.to(self.device)
