@@ -323,3 +323,161 @@ def folded_sphere(level=4, cap=0.5, depth=2.3, axis=(0.3, 0.5, 0.81)):
     t = np.clip((vs @ d / rad - (1.0 - cap)) / cap, 0.0, 1.0)          # 0 at the rim and below, 1 at the pole
     vs -= (depth * rad * np.sin(0.5 * np.pi * t) ** 2)[:, None] * d[None, :]
     return vs.astype(np.float32), np.asarray(m.faces, np.int64)
+
+
+# ---- degenerate soups: every slot, axis and winding of the predicate -------------------------------------------------------
+SPACING = 32                # between cluster centres; a cluster's coordinates stay within +-12 of its centre
+
+FLATNESS = ("generic", "z in {0, 1}", "z = 0", "z = x + y", "z = x")
+
+
+def signed_axis_permutations():
+    """The 48 maps x -> sign * x[perm] of the cube onto itself, as (perm, sign) pairs of int64 [3]."""
+    import itertools
+    return [(np.array(p, np.int64), np.array(s, np.int64)) for p in itertools.permutations(range(3))
+            for s in itertools.product((1, -1), repeat=3)]
+
+
+def cluster_centres(n, spacing=SPACING):
+    """int64 [n, 3]: the first n points of a cubic grid of that spacing, centred on the origin."""
+    side = 1
+    while side ** 3 < n:
+        side += 1
+    g = np.stack(np.unravel_index(np.arange(n), (side, side, side)), 1).astype(np.int64)
+    return (2 * g - (side - 1)) * (spacing // 2)
+
+
+def _assemble(clusters, spacing=SPACING):
+    """[(vs, faces)] of integer clusters -> one mesh, cluster c moved to the c-th grid centre; also the first face of each."""
+    centres = cluster_centres(len(clusters), spacing)
+    vs, faces, first, nv, nf = [], [], [], 0, 0
+    for (v, f), c in zip(clusters, centres):
+        assert np.abs(v).max() <= 12
+        vs.append(v + c)
+        faces.append(f + nv)
+        first.append(nf)
+        nv += v.shape[0]
+        nf += f.shape[0]
+    vs = np.concatenate(vs).astype(np.int64)
+    assert np.abs(vs).max() <= 2 ** 10
+    return vs, np.concatenate(faces).astype(np.int64), np.asarray(first + [nf], np.int64)
+
+
+def soup_cluster(c, rng, R=3, n_vertices=7, n_faces=12):
+    """Cluster c of soup_clusters about the origin: (vs int64 [7, 3], faces int64 [12, 3])."""
+    v = rng.integers(-R, R + 1, (n_vertices, 3))
+    kind = c % len(FLATNESS)
+    if kind == 1:
+        v[:, 2] = rng.integers(0, 2, n_vertices)
+    elif kind == 2:
+        v[:, 2] = 0
+    elif kind == 3:
+        v[:, 2] = v[:, 0] + v[:, 1]                          # normal (1, 1, -1): all three axes tie
+    elif kind == 4:
+        v[:, 2] = v[:, 0]                                   # normal (1, 0, -1): two axes tie
+    f = np.stack([rng.choice(n_vertices, 3, replace=(c % 8 == 7)) for _ in range(n_faces)])
+    perm, sign = signed_axis_permutations()[c % 48]
+    v = v[:, perm] * sign
+    if c % 2:
+        f = f[:, ::-1]
+    return v.astype(np.int64), np.ascontiguousarray(f).astype(np.int64)
+
+
+def soup_clusters(n=125, seed=2024, R=3, n_vertices=7, n_faces=12):
+    """n random triangle soups of 7 integer vertices in [-R, R]^3 and 12 faces each, on a grid of spacing 32 so that the
+    boxes of two clusters cannot touch: (vs int64, faces int64); cluster c owns vertices 7 c .. 7 c + 6 and faces
+    12 c .. 12 c + 11.  Faces draw 3 of the 7 ids without repetition, in every eighth cluster with (repeated ids).  The
+    flatness cycles through FLATNESS; cluster c is then mapped through the (c mod 48)-th signed axis permutation and
+    every second cluster has the winding of its faces reversed.  |coordinates| <= 2^10.  Seed 2024 is the first one
+    tried; tests/test_intersect_exact.py asserts what it has to provide."""
+    rng = np.random.default_rng(seed)
+    vs, faces, _ = _assemble([soup_cluster(c, rng, R, n_vertices, n_faces) for c in range(n)])
+    return vs, faces
+
+
+ORBIT_MAPS = (((2, 0, 1), (1, 1, 1)),         # (x, y, z) -> (z, x, y): the plane z = 0 becomes x = 0
+              ((1, 2, 0), (-1, 1, 1)),        # (x, y, z) -> (-y, z, x): z = 0 becomes y = 0
+              ((1, 0, 2), (1, 1, 1)))         # (x, y, z) -> (y, x, z): z = 0 stays, mirrored
+
+
+def hand_case_orbit():
+    """Every hand case in every labelling: (vs int64, faces, pairs int64 [P, 2], n_degenerate), the pairs and the count
+    by hand (relabelled), not from any oracle.  Two-face cases: the 6 vertex orders of face 0 x the 6 of face 1 x both
+    face orders; degenerate_faces: its 6 face orders x 6 vertex orders (face m takes order p + m).  The whole set three
+    times, under ORBIT_MAPS.  Each variant is a cluster of its own on the grid of soup_clusters."""
+    import itertools
+    orders = list(itertools.permutations(range(3)))
+    clusters, pairs, n_deg, nf = [], [], 0, 0
+    for perm, sign in ORBIT_MAPS:
+        for name, (v, f, want, d) in hand_cases().items():
+            v = v[:, list(perm)] * np.array(sign)
+            if f.shape[0] == 2:
+                variants = [((a, b), fo) for a in range(6) for b in range(6) for fo in ((0, 1), (1, 0))]
+            else:
+                variants = [(tuple((p + m) % 6 for m in range(3)), fo) for p in range(6)
+                            for fo in itertools.permutations(range(3))]
+            for vo, fo in variants:
+                g = np.stack([f[m][list(orders[vo[m]])] for m in range(f.shape[0])])[list(fo)]   # new face k = old fo[k]
+                new_of_old = np.argsort(fo)
+                for i, j in want.tolist():
+                    pairs.append(sorted((nf + int(new_of_old[i]), nf + int(new_of_old[j]))))
+                clusters.append((v, g))
+                n_deg += d
+                nf += g.shape[0]
+    vs, faces, _ = _assemble(clusters)
+    pairs = np.asarray(sorted(pairs), np.int64).reshape(-1, 2)
+    return vs, faces, pairs, n_deg
+
+
+def dyadic(vs, offset=(3.5, -1.25, 0.75)):
+    """Integer coordinates x 2^-7 plus a dyadic offset, float32: not integers, and every determinant still exact."""
+    out = np.asarray(vs, np.float64) * 2.0 ** -7 + np.asarray(offset, np.float64)
+    assert np.array_equal(out.astype(np.float32).astype(np.float64), out)
+    return out.astype(np.float32)
+
+
+def shifted_to_limit(vs, sign):
+    """Integer vs translated so that on every axis the largest (sign = +1) or smallest (-1) coordinate is +-1024: the
+    documented edge of the exactness claim."""
+    vs = np.asarray(vs, np.int64)
+    out = vs + (1024 - vs.max(0) if sign > 0 else -1024 - vs.min(0))
+    assert np.abs(out).max() == 1024
+    return out
+
+
+def rotated_soups(n=96, seed=2024):
+    """The soups of soup_clusters(n, seed) through a fixed rotation (0.6 rad about z, then 1.1 rad about x) x 1/3 plus
+    (2.25, -1.5, 3.125), rounded to float32: what was an exact zero determinant is rounding noise now."""
+    vs, faces = soup_clusters(n, seed)
+    a, b = 0.6, 1.1
+    Rz = np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
+    Rx = np.array([[1.0, 0.0, 0.0], [0.0, np.cos(b), -np.sin(b)], [0.0, np.sin(b), np.cos(b)]])
+    out = vs.astype(np.float64) @ (Rx @ Rz).T / 3.0 + np.array([2.25, -1.5, 3.125])
+    return out.astype(np.float32), faces
+
+
+def coincident_stack(K=70):
+    """K copies of one triangle, each with three vertex rows of its own: nothing is shared by id, every Morton code is
+    equal, every leaf box is the same, and all K (K - 1) / 2 pairs cross (face 0 has K - 1 partners above it)."""
+    tri = np.array([[0, 0, 0], [8, 0, 0], [0, 8, 3]], np.int64)
+    return np.tile(tri, (K, 1)), np.arange(3 * K, dtype=np.int64).reshape(K, 3)
+
+
+def ladder(big_first, steps=21):
+    """Triangles (s, s, s), (1.25 s, s, s), (s, 1.25 s, s) with s = 2^-k, k = 0 .. steps - 1, and one triangle (0, 0, 0),
+    (1.25, 0.75, 1), (0.75, 1.25, 1) whose median is the diagonal they all start on, as the first or the last face.
+    The centroids halve at every step, so the Morton tree degenerates towards a chain.  float32, all dyadic."""
+    vs, faces = [], []
+    for k in range(steps):
+        s = 2.0 ** -k
+        vs += [[s, s, s], [1.25 * s, s, s], [s, 1.25 * s, s]]
+        faces.append([3 * k, 3 * k + 1, 3 * k + 2])
+    big = [[0.0, 0.0, 0.0], [1.25, 0.75, 1.0], [0.75, 1.25, 1.0]]
+    if big_first:
+        vs, faces = big + vs, [[0, 1, 2]] + [[i + 3 for i in f] for f in faces]
+    else:
+        faces.append([3 * steps, 3 * steps + 1, 3 * steps + 2])
+        vs += big
+    out = np.asarray(vs, np.float64)
+    assert np.array_equal(out.astype(np.float32).astype(np.float64), out)
+    return out.astype(np.float32), np.asarray(faces, np.int64)

@@ -5,13 +5,23 @@ here), so the sign of every determinant is beyond doubt; there is no tolerance a
 Shapes: the hand cases (one per branch of the predicate, F = 2 or 3: a lone leaf); two interpenetrating cubes with F = 299
 (a partial leaf, a partial wavefront, five workgroups), also under a face permutation; a flat grid (all coplanar); a rounded
 torus and sphere (clean); two jittered tori of 6 080 faces in float32; one face with 1 200 partners, as the first face and
-as the last; and the repair loop on a folded sphere."""
+as the last; and the repair loop on a folded sphere.
+
+The restatement repeats the predicate branch by branch, so the second half of this file holds the device to
+tests/exact_intersect.py as well, the exact rational definition of "two faces cross" (tests/test_intersect_exact.py
+shows that the two agree on these inputs and that the inputs fill every class): 125 degenerate integer soups in every
+signed axis permutation, winding and flatness, whole, under a face permutation and as lone trees of F = 1 .. 12; the
+hand cases in every vertex order, face order and coordinate plane against the hand answers; the soups as dyadic
+floats and at |coordinate| = 1024; 70 coincident triangles (equal Morton codes) and a ladder of halving triangles (a
+chain-like tree), with the per-face counts and the walk's statistics; and rotated soups in float32 whose marginal
+determinants pin float64, the written order of operations and the absence of fused multiply-adds."""
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+import exact_intersect as EX
 import intersect_oracle as IO
 from semigcn_amd import synth
 
@@ -186,3 +196,135 @@ def test_a_clean_mesh_comes_back_as_it_is():
     out_vs, out_faces, report = repair.repair((dev(vs), dev(faces)))
     assert report.rounds == 0 and report.remaining == 0
     assert out_vs.cpu().numpy().tobytes() == vs.tobytes() and out_faces.cpu().numpy().tobytes() == faces.tobytes()
+
+
+# ---- every slot, axis and winding: the exact definition ---------------------------------------------------------------------
+SUBSET = 12 * 40           # the faces of the first 40 clusters: what the exact definition is run on where a part suffices
+
+
+@functools.lru_cache(maxsize=None)
+def soups():
+    vs, faces = IO.soup_clusters(125)
+    return vs, faces, IO.self_intersections(vs, faces)
+
+
+def check_exact(vs, faces):
+    """self_intersections on the device equals the exact definition: bytes of pairs and mask, and the count."""
+    pairs, n_degenerate = EX.self_intersections_exact(vs, faces)
+    got = detect(vs, faces)
+    mask = np.zeros(faces.shape[0], bool)
+    mask[pairs.reshape(-1)] = True
+    assert got.pairs.cpu().numpy().tobytes() == pairs.tobytes()
+    assert got.face_mask.cpu().numpy().tobytes() == mask.tobytes()
+    assert got.n_degenerate == n_degenerate
+    return got
+
+
+def check_counts(vs, faces, want):
+    """The count pass on its own: per-face counts equal the bincounts of the expected pairs; no subtree was dropped."""
+    from semigcn_amd import evaluate
+    s = evaluate.Surface(dev(vs, torch.float32), dev(faces))
+    try:
+        n_any, n_upper, stats = s._h.self_count(s.vs, s.faces)
+        torch.cuda.synchronize()
+    finally:
+        s.close()
+    assert np.array_equal(n_any.cpu().numpy(), np.bincount(want.pairs.reshape(-1), minlength=faces.shape[0]))
+    assert np.array_equal(n_upper.cpu().numpy(), np.bincount(want.pairs[:, 0], minlength=faces.shape[0]))
+    assert stats.tolist() == [want.n_degenerate, 0]
+
+
+def test_soups_equal_the_restatement_and_the_exact_definition():
+    vs, faces, want = soups()
+    assert len(want) > 2000 and want.n_degenerate > 0
+    check(vs, faces, want)
+    check_exact(vs, faces[:SUBSET])
+    check_counts(vs, faces, want)
+
+
+def test_soups_repeat_bit_for_bit():
+    vs, faces, _ = soups()
+    one, two = detect(vs, faces), detect(vs, faces)
+    assert one.pairs.cpu().numpy().tobytes() == two.pairs.cpu().numpy().tobytes() and len(one) > 0
+    assert one.face_mask.cpu().numpy().tobytes() == two.face_mask.cpu().numpy().tobytes()
+    assert one.n_degenerate == two.n_degenerate
+
+
+def test_soups_under_a_face_permutation():
+    vs, faces, want = soups()
+    perm = np.random.default_rng(11).permutation(faces.shape[0])      # new face k is old face perm[k]
+    got = detect(vs, faces[perm])
+    back = np.sort(perm[got.pairs.cpu().numpy()], 1)
+    back = back[np.lexsort((back[:, 1], back[:, 0]))]
+    assert np.array_equal(back, want.pairs)
+    assert np.array_equal(got.face_mask.cpu().numpy(), want.face_mask[perm]) and got.n_degenerate == want.n_degenerate
+
+
+@pytest.mark.parametrize("F", [1, 4, 5, 8, 9, 12])
+def test_one_soup_alone_is_a_tiny_tree(F):
+    """One, two and three leaves of four faces, full and partial: a generic soup, one in a coordinate plane and one with
+    repeated ids, each as a mesh of its own."""
+    vs, faces, _ = soups()
+    for c in (0, 2, 7):
+        v, f = vs[7 * c:7 * c + 7], faces[12 * c:12 * c + F] - 7 * c
+        check(v, f)
+        check_exact(v, f)
+
+
+def test_hand_cases_in_every_labelling_and_plane():
+    vs, faces, pairs, n_degenerate = IO.hand_case_orbit()
+    got = detect(vs, faces)
+    mask = np.zeros(faces.shape[0], bool)
+    mask[pairs.reshape(-1)] = True
+    assert got.pairs.cpu().numpy().tobytes() == pairs.tobytes()
+    assert got.face_mask.cpu().numpy().tobytes() == mask.tobytes()
+    assert got.n_degenerate == n_degenerate
+
+
+def test_dyadic_floats():
+    vs, faces, want = soups()
+    fv = IO.dyadic(vs)
+    want_f = IO.self_intersections(fv, faces)
+    assert np.array_equal(want_f.pairs, want.pairs)
+    check(fv, faces, want_f)
+    check_exact(fv, faces[:SUBSET])
+    check_counts(fv, faces, want_f)
+
+
+@pytest.mark.parametrize("sign", [1, -1])
+def test_at_the_limit_of_exactness(sign):
+    vs, faces, want = soups()
+    lv = IO.shifted_to_limit(vs, sign)
+    check(lv, faces, want)                                # a translation changes no verdict
+    check_exact(lv, faces[:SUBSET])
+    check_counts(lv, faces, want)
+
+
+def test_coincident_triangles_have_equal_morton_codes():
+    vs, faces = IO.coincident_stack(70)
+    got, want = check(vs, faces)
+    assert len(got) == 70 * 69 // 2 and int((got.pairs[:, 0] == 0).sum()) == 69
+    check_exact(vs, faces)
+    check_counts(vs, faces, want)
+
+
+@pytest.mark.parametrize("big_first", [True, False])
+def test_ladder_of_halving_triangles(big_first):
+    vs, faces = IO.ladder(big_first)
+    got, want = check(vs, faces)
+    assert len(got) > 0
+    check_exact(vs, faces)
+    check_counts(vs, faces, want)
+
+
+def test_rotated_soups_pin_float64_and_the_order_of_operations():
+    """Hundreds of candidate pairs here have a determinant that is rounding noise (tests/test_intersect_exact.py asserts
+    it, and that some verdicts differ from the exact rational ones): the device equals the restatement only by evaluating
+    in float64, in the written order, without fused multiply-adds.  Measured once: with csrc/mesh_isect.hip built
+    without -ffp-contract=off the device returns 950 of the 979 pairs here and this test fails, while the jittered tori
+    and the integer soups still pass."""
+    vs, faces = IO.rotated_soups(96)
+    want = IO.self_intersections(vs, faces)
+    assert len(want.marginal) >= 100
+    check(vs, faces, want)
+    check_counts(vs, faces, want)
