@@ -508,9 +508,9 @@ SG_API int sg_parts_emit(sg_parts* p, const float* vs, float* new_vs, int64_t* n
 
 /* ------------------------------------------------------------------------- *
  * Refining a mesh to a target edge length (csrc/mesh_remesh.hip): the edge
- * splits and edge flips of the isotropic remesh in the reference's
- * preprocess/prepare.py:35-42.  Edge collapse is not part of it.  The rules
- * (priority, selection, numbering of what is inserted, the flip guard) are
+ * splits, edge collapses and edge flips of the isotropic remesh in the
+ * reference's preprocess/prepare.py:35-42.  The rules (priority, selection,
+ * numbering of what is inserted, the guards, what a collapse keeps) are
  * specified in semigcn_amd/remesh.py.
  *
  * sg_remesh_create: takes a copy of vs float32 [V,3] and faces int64 [F,3]
@@ -523,7 +523,8 @@ SG_API int sg_parts_emit(sg_parts* p, const float* vs, float* new_vs, int64_t* n
  *   vertices with a non-finite coordinate, the smallest offending edge (lo, hi;
  *   -1, -1: none), the smallest offending face, the smallest offending vertex,
  *   V and F of the input, 1 when the input is valid (the four counts are 0),
- *   0 (reserved).  sg_remesh_split / sg_remesh_flip refuse an invalid input.
+ *   0 (reserved).  sg_remesh_split / sg_remesh_collapse / sg_remesh_flip refuse
+ *   an invalid input.
  * sg_remesh_split: rounds of edge splits until no edge has len2 > thr2 or
  *   max_rounds rounds ran.  counts (host, int64 [max_rounds]) receives the
  *   edges split per round, *n_rounds the rounds that split something, *n_long
@@ -533,6 +534,20 @@ SG_API int sg_parts_emit(sg_parts* p, const float* vs, float* new_vs, int64_t* n
  *   rounds ran.  counts (host, int64 [max_rounds]) receives the flips per round,
  *   deviation[2] (host) the sum of |valence - target| before and after.  One
  *   stream synchronisation per round.
+ * sg_remesh_collapse: rounds of edge collapses until none is selected or
+ *   max_rounds rounds ran: an interior edge with len2 < lo2 is collapsed into
+ *   one of its ends unless that would create an edge with len2 > thr2, fold a
+ *   face over, or change the topology.  Needs 0 < lo2 < thr2.  counts (host,
+ *   int64 [max_rounds]) receives the collapses per round, *n_rounds the rounds
+ *   that collapsed something, *n_short the edges with len2 < lo2 that are left.
+ *   Vertices and faces are renumbered (stable compaction); parents are remapped.
+ *   One stream synchronisation per round.
+ * sg_remesh_collapse_maps: for the last sg_remesh_collapse call, with V_before
+ *   and V' the vertex counts before and after it: vertex_ids int64 [V'] (device)
+ *   = the index each surviving vertex had before the call, merged_into int64
+ *   [V_before] (device) = the index after the call of the vertex that each
+ *   earlier vertex ended up in (its own new index when it survived).  Before any
+ *   collapse call both are the identity over the current V.  Asynchronous.
  * sg_remesh_export: writes the current mesh to device arrays of the caller:
  *   vs float32 [V,3], faces int64 [F,3], parents int64 [V,2] ((i, i) for a
  *   vertex of the input, the two ends (lo, hi) of the split edge otherwise) and,
@@ -546,6 +561,9 @@ SG_API int sg_remesh_query(const sg_remesh* p, int64_t* info);
 SG_API int sg_remesh_split(sg_remesh* p, float thr2, int64_t max_rounds, void* stream, int64_t* counts, int64_t* n_rounds,
                            int64_t* n_long);
 SG_API int sg_remesh_flip(sg_remesh* p, int64_t max_rounds, void* stream, int64_t* counts, int64_t* n_rounds, int64_t* deviation);
+SG_API int sg_remesh_collapse(sg_remesh* p, float lo2, float thr2, int64_t max_rounds, void* stream, int64_t* counts,
+                              int64_t* n_rounds, int64_t* n_short);
+SG_API int sg_remesh_collapse_maps(const sg_remesh* p, int64_t* vertex_ids, int64_t* merged_into, void* stream);
 SG_API int sg_remesh_export(const sg_remesh* p, float* vs, int64_t* faces, int64_t* parents, uint8_t* border, void* stream);
 
 /* ------------------------------------------------------------------------- *

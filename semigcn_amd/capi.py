@@ -223,6 +223,9 @@ _SIGNATURES = {
     "sg_remesh_query": (c_int, [c_void_p, POINTER(c_int64)]),
     "sg_remesh_split": (c_int, [c_void_p, c_float, c_int64, c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "sg_remesh_flip": (c_int, [c_void_p, c_int64, c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "sg_remesh_collapse": (c_int, [c_void_p, c_float, c_float, c_int64, c_void_p, POINTER(c_int64), POINTER(c_int64),
+                                   POINTER(c_int64)]),
+    "sg_remesh_collapse_maps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_remesh_export": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
@@ -1642,12 +1645,13 @@ class PartsPlan(_OwnedHandle):
 
 
 class RemeshPlan(_OwnedHandle):
-    """Owns one sg_remesh (csrc/mesh_remesh.hip): a copy of a mesh on the device that ``split`` and ``flip`` refine in place
+    """Owns one sg_remesh (csrc/mesh_remesh.hip): a copy of a mesh on the device that ``split``, ``collapse`` and ``flip`` refine in place
     (the rules are specified in semigcn_amd/remesh.py) and ``export`` hands back.  ``n_nonmanifold`` / ``n_misoriented`` /
     ``n_degenerate`` / ``n_nonfinite`` with ``bad_edge`` / ``bad_face`` / ``bad_vertex`` say why an input is refused;
-    ``split`` and ``flip`` then raise."""
+    ``split``, ``collapse`` and ``flip`` then raise."""
 
     _destroy = "sg_remesh_destroy"
+    _map_sizes = None                     # (V', V_before) of the last collapse call
 
     def __init__(self, vs: torch.Tensor, faces: torch.Tensor):
         _require_device(vs, "vs")
@@ -1706,6 +1710,35 @@ class RemeshPlan(_OwnedHandle):
             _check(load().sg_remesh_flip(self._h, max_rounds, _raw_stream_of(self.device), counts, byref(n_rounds), dev),
                    "sg_remesh_flip")
         return [int(c) for c in counts[: n_rounds.value]], int(dev[0]), int(dev[1])
+
+    def collapse(self, lo2: float, thr2: float, max_rounds: int = 128):
+        """(collapses per round, short edges left): rounds of edge collapses until none is selected or ``max_rounds``
+        rounds ran.  ``lo2`` and ``thr2`` are passed as float32.  Vertices and faces are renumbered."""
+        self._open()
+        max_rounds = int(max_rounds)
+        counts = (c_int64 * max(max_rounds, 1))()
+        n_rounds, n_short = c_int64(), c_int64()
+        before = self.num_vertices
+        with _on_device(self.device):
+            _check(load().sg_remesh_collapse(self._h, c_float(lo2), c_float(thr2), max_rounds, _raw_stream_of(self.device),
+                                             counts, byref(n_rounds), byref(n_short)), "sg_remesh_collapse")
+        self._sizes()
+        self._map_sizes = (self.num_vertices, before)
+        return [int(c) for c in counts[: n_rounds.value]], int(n_short.value)
+
+    def collapse_maps(self):
+        """(vertex_ids int64 [V'], merged_into int64 [V_before]) of the last ``collapse`` call: the index each surviving
+        vertex had before it, and the index after it of the vertex each earlier vertex ended up in.  Both are the identity
+        before any ``collapse``."""
+        self._open()
+        after, before = self._map_sizes or (self.num_vertices, self.num_vertices)
+        vertex_ids = torch.empty(after, dtype=torch.int64, device=self.device)
+        merged_into = torch.empty(before, dtype=torch.int64, device=self.device)
+        none_if_empty = lambda t: _ptr(t) if t.numel() else None
+        with _on_device(self.device):
+            _check(load().sg_remesh_collapse_maps(self._h, none_if_empty(vertex_ids), none_if_empty(merged_into),
+                                                  _raw_stream_of(self.device)), "sg_remesh_collapse_maps")
+        return vertex_ids, merged_into
 
     def export(self):
         """(vs float32 [V, 3], faces int64 [F, 3], parents int64 [V, 2], border bool [V]) of the mesh as it stands."""

@@ -642,7 +642,7 @@ SG_API int sg_parts_emit(sg_parts* p, const float* vs, float* new_vs, int64_t* n
   return parts_emit(p, vs, new_vs, new_faces, vertex_ids, face_ids, (hipStream_t)stream);
 }
 
-// splitting and flipping of the isotropic remesh (preprocess/prepare.py:35-42): csrc/mesh_remesh.hip
+// splitting, collapsing and flipping of the isotropic remesh (preprocess/prepare.py:35-42): csrc/mesh_remesh.hip
 SG_API int sg_remesh_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, void* stream, sg_remesh** out) {
   SG_REQUIRE(out != nullptr, "sg_remesh_create: null out");
   *out = nullptr;
@@ -677,6 +677,22 @@ SG_API int sg_remesh_flip(sg_remesh* p, int64_t max_rounds, void* stream, int64_
   SG_REQUIRE(max_rounds >= 0, "sg_remesh_flip: negative max_rounds (%lld)", (long long)max_rounds);
   SG_REQUIRE(n_rounds && deviation && (max_rounds == 0 || counts), "sg_remesh_flip: null pointer");
   return remesh_flip(p, max_rounds, (hipStream_t)stream, counts, n_rounds, deviation);
+}
+
+SG_API int sg_remesh_collapse(sg_remesh* p, float lo2, float thr2, int64_t max_rounds, void* stream, int64_t* counts,
+                              int64_t* n_rounds, int64_t* n_short) {
+  SG_REQUIRE(p != nullptr, "sg_remesh_collapse: null plan");
+  SG_REQUIRE(max_rounds >= 0, "sg_remesh_collapse: negative max_rounds (%lld)", (long long)max_rounds);
+  SG_REQUIRE(lo2 > 0.0f, "sg_remesh_collapse: lo2 must be positive");          // false for a NaN as well
+  SG_REQUIRE(thr2 > 0.0f, "sg_remesh_collapse: thr2 must be positive");
+  SG_REQUIRE(lo2 < thr2, "sg_remesh_collapse: lo2 must be below thr2");
+  SG_REQUIRE(n_rounds && n_short && (max_rounds == 0 || counts), "sg_remesh_collapse: null pointer");
+  return remesh_collapse(p, lo2, thr2, max_rounds, (hipStream_t)stream, counts, n_rounds, n_short);
+}
+
+SG_API int sg_remesh_collapse_maps(const sg_remesh* p, int64_t* vertex_ids, int64_t* merged_into, void* stream) {
+  SG_REQUIRE(p != nullptr, "sg_remesh_collapse_maps: null plan");
+  return remesh_collapse_maps(p, vertex_ids, merged_into, (hipStream_t)stream);
 }
 
 SG_API int sg_remesh_export(const sg_remesh* p, float* vs, int64_t* faces, int64_t* parents, uint8_t* border, void* stream) {

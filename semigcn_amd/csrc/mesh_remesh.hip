@@ -1,8 +1,8 @@
-// Refining a triangle mesh to a target edge length on the device: split long edges, flip edges towards regular valence.
+// Refining a triangle mesh to a target edge length on the device: split long edges, collapse short ones, flip edges towards
+// regular valence.
 //
-// Replaces the splitting and flipping of the isotropic remesh the reference runs between MeshFix and the scaling
-// (preprocess/prepare.py:35-42); edge collapse is not part of it, and the relaxation / re-projection is plumbing over
-// mesh_smooth.hip and mesh_dist.hip.  The specification is semigcn_amd/remesh.py; in short:
+// Replaces the splitting, collapsing and flipping of the isotropic remesh the reference runs between MeshFix and the scaling
+// (preprocess/prepare.py:35-42); the relaxation / re-projection is plumbing over mesh_smooth.hip and mesh_dist.hip.  The specification is semigcn_amd/remesh.py; in short:
 //
 //   analysis   every round starts from the same analysis of the mesh it finds: half-edge h = 3 f + k is keyed lo * V + hi
 //              (undirected) with h as the value; one radix sort over the 3 F pairs, restricted to the bits V * V needs, puts
@@ -18,6 +18,15 @@
 //              a 64-bit atomicMax of the key into the slot of each of the four vertices; a check pass (a candidate wins when
 //              all four slots hold its key); ONE host synchronisation reads the number of winners and the deviation; the
 //              apply pass rewrites the two faces of every winner.  Winners are vertex-disjoint, hence face-disjoint.
+//   collapse   the analysis also records the twin of every half-edge.  Candidate pass: one lane per interior short edge walks
+//              the fan of the removed vertex r through twin and next half-edges -- a counted loop of val[r] steps -- looks
+//              every {k, w} up in the sorted keys, evaluates the guards and bids (0xFFFFFFFF - len2 bits) << 32 | hash(r) by
+//              64-bit atomicMax into the slot of every vertex of its footprint {r} + ring(r); the check pass walks the same
+//              fan (a candidate wins when every slot holds its key); ONE host synchronisation reads the winners and the
+//              short edges; the apply pass marks the two faces of the edge and r dead and writes k over r in the other faces
+//              at r; two exclusive scans over the keep flags; the compaction writes vs / par / tri / border into second
+//              buffers (stable), which are then swapped in, and composes the vertex maps of the call.  A collapse reads and
+//              writes only inside its footprint, so footprint-disjoint winners are independent.
 //
 // hash is the 32-bit mixer x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16: a bijection, so two
 // edges never tie and the order in which the atomics arrive cannot matter.  There are no float atomics; integer max and
@@ -35,7 +44,7 @@ namespace {
 // slots of the counter block
 enum {
   kOutOfRange = 0, kDegenerate, kBadFace, kNonFinite, kBadVertex, kNonManifold, kMisoriented, kBadKey, kBorderEdges, kEdges,
-  kLong, kWinners, kDeviation, kTotalA, kTotalF, kCounters = 16
+  kLong, kWinners, kDeviation, kTotalA, kTotalF, kShort, kCounters = 16
 };
 
 }  // namespace
@@ -54,6 +63,12 @@ struct sg_remesh {
   sg::GrowBuf<unsigned long long> cand, slot, ctr;
   sg::GrowBuf<uint8_t> win;
   sg::GrowBuf<char> temp;
+  // collapse: the twin of every half-edge, keep flags and their scans over the vertices, where a removed vertex went, the
+  // second buffers the compaction writes, and the maps of the last collapse call (ids: new -> before, into: before -> new)
+  sg::GrowBuf<int32_t> twin, flag_v, scan_v, dest, par2, tri2, ids, ids2, into;
+  sg::GrowBuf<float> vs2;
+  sg::GrowBuf<uint8_t> border2;
+  int64_t map_before = -1, map_after = -1;          // sizes of the maps; -1: no collapse call yet, both are the identity
 };
 
 namespace sg {
@@ -139,11 +154,12 @@ __device__ inline int run_length(const int32_t* __restrict__ head, int64_t p, in
   return 3;
 }
 
-// he_rank[h] = rank of h's edge; per edge: the validation counts, border vertices and (val != null) the valences
+// he_rank[h] = rank of h's edge; per edge: the validation counts, border vertices, (val != null) the valences and
+// (twin != null) the other half-edge of the run, -1 on a border edge
 __global__ void edge_pass(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals, const int32_t* __restrict__ head,
                           const int32_t* __restrict__ incl, int64_t n, int64_t F, int64_t V, const int32_t* __restrict__ tri,
                           int32_t* __restrict__ he_rank, uint8_t* __restrict__ border, int32_t* __restrict__ val,
-                          unsigned long long* __restrict__ ctr) {
+                          int32_t* __restrict__ twin, unsigned long long* __restrict__ ctr) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
   const int32_t h = vals[p];
@@ -164,8 +180,13 @@ __global__ void edge_pass(const uint64_t* __restrict__ keys, const int32_t* __re
     atomicAdd(&ctr[kBorderEdges], 1ull);
     border[a] = 1;                                   // every writer stores the same 1
     border[b] = 1;
+    if (twin) twin[h] = -1;
   } else if (len == 2) {
     const int32_t h1 = vals[p + 1];
+    if (twin && h1 >= 0 && h1 < n) {
+      twin[h] = h1;
+      twin[h1] = h;
+    }
     if (h1 >= 0 && h1 < n && tri[h1] == a) {         // both faces run the edge from a: not opposite
       atomicAdd(&ctr[kMisoriented], 1ull);
       atomicMin(&ctr[kBadKey], (unsigned long long)keys[p]);
@@ -397,10 +418,217 @@ __global__ void flip_apply(const uint8_t* __restrict__ win, const int32_t* __res
   tri[3 * f1 + 2] = q[2];
 }
 
+// ---- collapse -------------------------------------------------------------------------------------------------------------
+// is {a, b} an edge of the round's mesh: lower bound in the sorted keys
+__device__ inline bool has_edge(const uint64_t* __restrict__ keys, int64_t n, int64_t V, int32_t a, int32_t b) {
+  const uint64_t want = (uint64_t)(a < b ? a : b) * (uint64_t)V + (uint64_t)(a < b ? b : a);
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < want) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < n && keys[lo] == want;
+}
+
+// the interior edge whose run starts at p: the kept vertex k, the removed vertex r and the half-edge from r to k; false when
+// both ends are border vertices
+__device__ inline bool collapse_ends(const int32_t* __restrict__ vals, const int32_t* __restrict__ tri,
+                                     const uint8_t* __restrict__ border, int64_t p, int32_t& k, int32_t& r, int32_t& hs) {
+  const int32_t h0 = vals[p], h1 = vals[p + 1];
+  const int64_t f0 = h0 / 3;
+  const int32_t a = tri[h0], b = tri[3 * f0 + next3((int)(h0 - 3 * f0))];
+  const bool ba = border[a] != 0, bb = border[b] != 0;
+  if (ba && bb) return false;
+  k = ba ? a : (bb ? b : (a < b ? a : b));
+  r = k == a ? b : a;
+  hs = r == a ? h0 : h1;                              // h0 runs from a to b, h1 from b to a: the mesh was validated
+  return true;
+}
+
+// One step of the walk round r: h runs from r to w in the face (r, w, y); the next half-edge from r is the twin of the one
+// from y to r.  -1 when there is none (never for an interior r of a valid mesh): the caller ends its walk.
+__device__ inline int32_t fan_step(const int32_t* __restrict__ tri, const int32_t* __restrict__ twin, int64_t n, int32_t h,
+                                   int32_t& w, int32_t& y) {
+  const int64_t f = h / 3;
+  const int j = (int)(h - 3 * f);
+  const int jp = next3(next3(j));
+  w = tri[3 * f + next3(j)];
+  y = tri[3 * f + jp];
+  const int32_t t = twin[3 * f + jp];
+  return (t >= 0 && t < n) ? t : -1;
+}
+
+__device__ inline int valence_floor(const uint8_t* __restrict__ border, int32_t v) { return border[v] ? 2 : 3; }
+
+// cand[p] = (0xFFFFFFFF - len2 bits) << 32 | hash(rank) for a candidate, 0 otherwise; counts the short edges; every candidate
+// bids for the vertices of its footprint.  Both walks are counted loops of val[r] steps.
+__global__ void collapse_candidates(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals,
+                                    const int32_t* __restrict__ head, const int32_t* __restrict__ incl,
+                                    const int32_t* __restrict__ twin, int64_t n, int64_t V, const int32_t* __restrict__ tri,
+                                    const float* __restrict__ vs, const int32_t* __restrict__ val,
+                                    const uint8_t* __restrict__ border, float lo2, float thr2,
+                                    unsigned long long* __restrict__ cand, unsigned long long* __restrict__ slot,
+                                    unsigned long long* __restrict__ ctr) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  unsigned long long key = 0;
+  if (head[p]) {
+    const int32_t h0 = vals[p];
+    const int64_t f0 = h0 / 3;
+    const int k0 = (int)(h0 - 3 * f0);
+    const float l2 = edge_len2(vs, tri[h0], tri[3 * f0 + next3(k0)]);
+    int32_t k = 0, r = 0, hs = 0;
+    if (l2 < lo2) {
+      atomicAdd(&ctr[kShort], 1ull);
+      bool ok = run_length(head, p, n) == 2 && collapse_ends(vals, tri, border, p, k, r, hs);
+      int vr = 0;
+      if (ok) {
+        const int32_t h1 = vals[p + 1];
+        const int64_t f1 = h1 / 3;
+        const int32_t c = tri[3 * f0 + next3(next3(k0))], d = tri[3 * f1 + next3(next3((int)(h1 - 3 * f1)))];
+        vr = val[r];
+        ok = c != d && val[c] - 1 >= valence_floor(border, c) && val[d] - 1 >= valence_floor(border, d) &&
+             val[k] + vr - 4 >= valence_floor(border, k);
+      }
+      if (ok) {
+        int links = 0;
+        int32_t h = hs;
+        for (int i = 0; i < vr && ok; ++i) {
+          int32_t w, y;
+          const int32_t t = fan_step(tri, twin, n, h, w, y);
+          if (w != k) {
+            if (has_edge(keys, n, V, k, w)) ++links;
+            if (edge_len2(vs, k, w) > thr2) ok = false;                    // the split stage would split {k, w}
+            if (y != k) {                                                  // the face (r, w, y) becomes (k, w, y)
+              const D3 nr = cross3(sub3(vs, w, r), sub3(vs, y, r)), nk = cross3(sub3(vs, w, k), sub3(vs, y, k));
+              if (!(dot3(nr, nk) > 0.0)) ok = false;
+            }
+          }
+          if (t < 0 || (t == hs) != (i + 1 == vr)) ok = false;             // the fan is one closed cycle of val[r] faces
+          h = t < 0 ? hs : t;
+        }
+        ok = ok && links == 2;
+      }
+      if (ok) {
+        key = ((unsigned long long)(0xFFFFFFFFu - __float_as_uint(l2)) << 32) | hash32((uint32_t)(incl[p] - 1));
+        atomicMax(slot + r, key);
+        int32_t h = hs;
+        for (int i = 0; i < vr; ++i) {
+          int32_t w, y;
+          const int32_t t = fan_step(tri, twin, n, h, w, y);
+          atomicMax(slot + w, key);
+          if (t < 0) break;
+          h = t;
+        }
+      }
+    }
+  }
+  cand[p] = key;
+}
+
+__global__ void collapse_check(const unsigned long long* __restrict__ cand, const int32_t* __restrict__ vals,
+                               const int32_t* __restrict__ twin, const int32_t* __restrict__ tri, const int32_t* __restrict__ val,
+                               const uint8_t* __restrict__ border, const unsigned long long* __restrict__ slot, int64_t n,
+                               uint8_t* __restrict__ win, unsigned long long* __restrict__ ctr) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const unsigned long long key = cand[p];
+  uint8_t w8 = 0;
+  int32_t k, r, hs;
+  if (key && collapse_ends(vals, tri, border, p, k, r, hs)) {
+    bool all = slot[r] == key;
+    const int vr = val[r];
+    int32_t h = hs;
+    for (int i = 0; i < vr && all; ++i) {
+      int32_t w, y;
+      const int32_t t = fan_step(tri, twin, n, h, w, y);
+      all = slot[w] == key && t >= 0;
+      h = t < 0 ? hs : t;
+    }
+    w8 = all ? 1 : 0;
+    if (w8) atomicAdd(&ctr[kWinners], 1ull);
+  }
+  win[p] = w8;
+}
+
+__global__ void fill_ones(int32_t* __restrict__ flag, int64_t n) {       // flag[0 .. n) = 1, flag[n] = 0
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i <= n) flag[i] = i < n ? 1 : 0;
+}
+
+// per winner: its two faces and r are dropped, dest[r] = k, and k goes into r's slot of the other faces at r
+__global__ void collapse_apply(const uint8_t* __restrict__ win, const int32_t* __restrict__ vals, const int32_t* __restrict__ twin,
+                               const int32_t* __restrict__ val, const uint8_t* __restrict__ border, int64_t n, int64_t F,
+                               int32_t* __restrict__ tri, int32_t* __restrict__ flag_f, int32_t* __restrict__ flag_v,
+                               int32_t* __restrict__ dest) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n || !win[p]) return;
+  int32_t k, r, hs;
+  if (!collapse_ends(vals, tri, border, p, k, r, hs)) return;
+  flag_v[r] = 0;
+  dest[r] = k;
+  const int vr = val[r];
+  int32_t h = hs;
+  for (int i = 0; i < vr; ++i) {
+    int32_t w, y;
+    const int32_t t = fan_step(tri, twin, n, h, w, y);
+    if (w == k || y == k) flag_f[h / 3] = 0;
+    else tri[h] = k;                                   // h starts at r
+    if (t < 0) break;
+    h = t;
+  }
+}
+
+__device__ inline int32_t new_vertex(const int32_t* __restrict__ flag_v, const int32_t* __restrict__ scan_v,
+                                     const int32_t* __restrict__ dest, int32_t v) {
+  return flag_v[v] ? scan_v[v] : scan_v[dest[v]];      // the kept end of a winner survives its round
+}
+
+__global__ void compact_vertices(const int32_t* __restrict__ flag_v, const int32_t* __restrict__ scan_v,
+                                 const int32_t* __restrict__ dest, int64_t V, int64_t V2, const float* __restrict__ vs,
+                                 const int32_t* __restrict__ par, const uint8_t* __restrict__ border, const int32_t* __restrict__ ids,
+                                 float* __restrict__ vs2, int32_t* __restrict__ par2, uint8_t* __restrict__ border2,
+                                 int32_t* __restrict__ ids2) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V || !flag_v[v]) return;
+  const int64_t m = scan_v[v];
+  if (m < 0 || m >= V2) return;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) vs2[3 * m + i] = vs[3 * v + i];
+  par2[2 * m] = new_vertex(flag_v, scan_v, dest, par[2 * v]);
+  par2[2 * m + 1] = new_vertex(flag_v, scan_v, dest, par[2 * v + 1]);
+  border2[m] = border[v];
+  ids2[m] = ids[v];
+}
+
+__global__ void compact_faces(const int32_t* __restrict__ flag_f, const int32_t* __restrict__ scan_f,
+                              const int32_t* __restrict__ scan_v, int64_t F, int64_t F2, const int32_t* __restrict__ tri,
+                              int32_t* __restrict__ tri2) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= F || !flag_f[f]) return;
+  const int64_t g = scan_f[f];
+  if (g < 0 || g >= F2) return;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) tri2[3 * g + i] = scan_v[tri[3 * f + i]];   // every vertex of a kept face is kept
+}
+
+__global__ void compose_into(const int32_t* __restrict__ flag_v, const int32_t* __restrict__ scan_v,
+                             const int32_t* __restrict__ dest, int64_t n_before, int32_t* __restrict__ into) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_before) into[i] = new_vertex(flag_v, scan_v, dest, into[i]);
+}
+
+template <class T>
+__global__ void iota(T* __restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (T)i;
+}
+
 // ---- host -------------------------------------------------------------------------------------------------------------------
 // keys, sort, heads, ranks, edge pass on the mesh as it stands; resets the counters first.  No host synchronisation unless a
 // scratch buffer has to grow.
-int analyse(sg_remesh* s, bool with_valence, hipStream_t stream) {
+int analyse(sg_remesh* s, bool with_valence, hipStream_t stream, bool with_twin = false) {
   const int64_t V = s->V, F = s->F, n = 3 * F;
   for (auto* b : {&s->keys_a, &s->keys_b})
     if (int rc = b->reserve(n, false, stream)) return rc;
@@ -414,6 +642,8 @@ int analyse(sg_remesh* s, bool with_valence, hipStream_t stream) {
   if (int rc = s->win.reserve(n, false, stream)) return rc;
   if (int rc = s->slot.reserve(V, false, stream)) return rc;
   if (int rc = s->val.reserve(V, false, stream)) return rc;
+  if (with_twin)
+    if (int rc = s->twin.reserve(n, false, stream)) return rc;
   const int bits = bits_for((uint64_t)V * (uint64_t)V, 62);    // the keys are below V * V < 2^62
   const int32_t *head = s->head.p, *flag_a = s->flag_a.p, *flag_f = s->flag_f.p;   // hipCUB's iterator arguments keep their const
   size_t tb_sort = 0, tb_incl = 0, tb_a = 0, tb_f = 0;
@@ -439,7 +669,8 @@ int analyse(sg_remesh* s, bool with_valence, hipStream_t stream) {
   tb_use = s->temp.cap;
   SG_HIP_TRY(hipcub::DeviceScan::InclusiveSum(s->temp.p, tb_use, head, s->incl.p, (int)n, stream));
   edge_pass<<<blocks_for(n), kThreads, 0, stream>>>(s->keys_b.p, s->vals_b.p, s->head.p, s->incl.p, n, F, V, s->tri.p,
-                                                   s->he_rank.p, s->border.p, with_valence ? s->val.p : nullptr, s->ctr.p);
+                                                   s->he_rank.p, s->border.p, with_valence ? s->val.p : nullptr,
+                                                   with_twin ? s->twin.p : nullptr, s->ctr.p);
   SG_HIP_TRY(hipGetLastError());
   return SG_OK;
 }
@@ -585,6 +816,106 @@ int remesh_flip(sg_remesh* s, int64_t max_rounds, hipStream_t stream, int64_t* c
     counts[round] = W;
     *n_rounds = round + 1;
   }
+  return SG_OK;
+}
+
+namespace {
+template <class T>
+void swap_bufs(GrowBuf<T>& a, GrowBuf<T>& b) {
+  std::swap(a.p, b.p);
+  std::swap(a.cap, b.cap);
+}
+
+}  // namespace
+
+int remesh_collapse(sg_remesh* s, float lo2, float thr2, int64_t max_rounds, hipStream_t stream, int64_t* counts,
+                    int64_t* n_rounds, int64_t* n_short) {
+  *n_rounds = 0;
+  *n_short = 0;
+  SG_REQUIRE(s->valid, "sg_remesh_collapse: the mesh did not pass validation (sg_remesh_query)");
+  s->map_before = s->map_after = s->V;
+  if (s->V == 0) return SG_OK;
+  const int64_t V_before = s->V;
+  if (int rc = s->ids.reserve(V_before, false, stream)) return rc;
+  if (int rc = s->into.reserve(V_before, false, stream)) return rc;
+  iota<<<blocks_for(V_before), kThreads, 0, stream>>>(s->ids.p, V_before);
+  iota<<<blocks_for(V_before), kThreads, 0, stream>>>(s->into.p, V_before);
+  SG_HIP_TRY(hipGetLastError());
+  if (s->F == 0) return SG_OK;
+  for (int64_t round = 0;; ++round) {
+    const int64_t V = s->V, F = s->F, n = 3 * F;
+    if (F == 0) {                                     // every face went: nothing left to analyse
+      *n_short = 0;
+      break;
+    }
+    if (int rc = analyse(s, true, stream, true)) return rc;
+    SG_HIP_TRY(hipMemsetAsync(s->slot.p, 0, (size_t)V * sizeof(uint64_t), stream));
+    collapse_candidates<<<blocks_for(n), kThreads, 0, stream>>>(s->keys_b.p, s->vals_b.p, s->head.p, s->incl.p, s->twin.p, n, V,
+                                                               s->tri.p, s->vs.p, s->val.p, s->border.p, lo2, thr2, s->cand.p,
+                                                               s->slot.p, s->ctr.p);
+    collapse_check<<<blocks_for(n), kThreads, 0, stream>>>(s->cand.p, s->vals_b.p, s->twin.p, s->tri.p, s->val.p, s->border.p,
+                                                          s->slot.p, n, s->win.p, s->ctr.p);
+    SG_HIP_TRY(hipGetLastError());
+    unsigned long long c[kCounters];
+    if (int rc = read_counters(s, c, stream)) return rc;       // the round's one synchronisation: count -> apply
+    const int64_t W = (int64_t)c[kWinners];
+    *n_short = (int64_t)c[kShort];
+    SG_REQUIRE(W >= 0 && W < V && 2 * W <= F, "sg_remesh_collapse: winner count %lld out of range", (long long)W);
+    if (W == 0 || round >= max_rounds) break;
+    const int64_t V2 = V - W, F2 = F - 2 * W;
+    for (auto* b : {&s->flag_v, &s->scan_v})
+      if (int rc = b->reserve(V + 1, false, stream)) return rc;
+    if (int rc = s->dest.reserve(V, false, stream)) return rc;
+    if (int rc = s->vs2.reserve(3 * V2, false, stream)) return rc;
+    if (int rc = s->par2.reserve(2 * V2, false, stream)) return rc;
+    if (int rc = s->border2.reserve(V2, false, stream)) return rc;
+    if (int rc = s->ids2.reserve(V2, false, stream)) return rc;
+    if (int rc = s->tri2.reserve(3 * F2, false, stream)) return rc;
+    const int32_t *flag_v = s->flag_v.p, *flag_f = s->flag_f.p;   // hipCUB's iterator arguments keep their const
+    size_t tb_v = 0;
+    SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_v, flag_v, s->scan_v.p, (int)(V + 1), stream));
+    if (int rc = s->temp.reserve(tb_v ? tb_v : 16, false, stream)) return rc;
+    fill_ones<<<blocks_for(V + 1), kThreads, 0, stream>>>(s->flag_v.p, V);
+    fill_ones<<<blocks_for(F + 1), kThreads, 0, stream>>>(s->flag_f.p, F);
+    collapse_apply<<<blocks_for(n), kThreads, 0, stream>>>(s->win.p, s->vals_b.p, s->twin.p, s->val.p, s->border.p, n, F,
+                                                          s->tri.p, s->flag_f.p, s->flag_v.p, s->dest.p);
+    SG_HIP_TRY(hipGetLastError());
+    size_t tb = s->temp.cap;
+    SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->temp.p, tb, flag_v, s->scan_v.p, (int)(V + 1), stream));
+    tb = s->temp.cap;
+    SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->temp.p, tb, flag_f, s->scan_f.p, (int)(F + 1), stream));
+    compact_vertices<<<blocks_for(V), kThreads, 0, stream>>>(s->flag_v.p, s->scan_v.p, s->dest.p, V, V2, s->vs.p, s->par.p,
+                                                            s->border.p, s->ids.p, s->vs2.p, s->par2.p, s->border2.p, s->ids2.p);
+    if (F2 > 0)
+      compact_faces<<<blocks_for(F), kThreads, 0, stream>>>(s->flag_f.p, s->scan_f.p, s->scan_v.p, F, F2, s->tri.p, s->tri2.p);
+    compose_into<<<blocks_for(V_before), kThreads, 0, stream>>>(s->flag_v.p, s->scan_v.p, s->dest.p, V_before, s->into.p);
+    SG_HIP_TRY(hipGetLastError());
+    swap_bufs(s->vs, s->vs2);
+    swap_bufs(s->par, s->par2);
+    swap_bufs(s->border, s->border2);
+    swap_bufs(s->ids, s->ids2);
+    swap_bufs(s->tri, s->tri2);
+    s->V = s->map_after = V2;
+    s->F = F2;
+    counts[round] = W;
+    *n_rounds = round + 1;
+  }
+  return SG_OK;
+}
+
+int remesh_collapse_maps(const sg_remesh* s, int64_t* vertex_ids, int64_t* merged_into, hipStream_t stream) {
+  const bool called = s->map_before >= 0;
+  const int64_t n_after = called ? s->map_after : s->V, n_before = called ? s->map_before : s->V;
+  SG_REQUIRE((n_after == 0 || vertex_ids) && (n_before == 0 || merged_into), "sg_remesh_collapse_maps: null pointer");
+  if (n_before == 0) return SG_OK;                  // nothing to write, no device to ask
+  if (called) {
+    if (n_after > 0) widen32<<<blocks_for(n_after), kThreads, 0, stream>>>(s->ids.p, n_after, vertex_ids);
+    widen32<<<blocks_for(n_before), kThreads, 0, stream>>>(s->into.p, n_before, merged_into);
+  } else {
+    iota<<<blocks_for(n_after), kThreads, 0, stream>>>(vertex_ids, n_after);
+    iota<<<blocks_for(n_before), kThreads, 0, stream>>>(merged_into, n_before);
+  }
+  SG_HIP_TRY(hipGetLastError());
   return SG_OK;
 }
 

@@ -397,6 +397,9 @@ void remesh_query(const sg_remesh* s, int64_t* info);
 int remesh_split(sg_remesh* s, float thr2, int64_t max_rounds, hipStream_t stream, int64_t* counts, int64_t* n_rounds,
                  int64_t* n_long);
 int remesh_flip(sg_remesh* s, int64_t max_rounds, hipStream_t stream, int64_t* counts, int64_t* n_rounds, int64_t* deviation);
+int remesh_collapse(sg_remesh* s, float lo2, float thr2, int64_t max_rounds, hipStream_t stream, int64_t* counts,
+                    int64_t* n_rounds, int64_t* n_short);
+int remesh_collapse_maps(const sg_remesh* s, int64_t* vertex_ids, int64_t* merged_into, hipStream_t stream);
 int remesh_export(const sg_remesh* s, float* vs, int64_t* faces, int64_t* parents, uint8_t* border, hipStream_t stream);
 
 // trace.hip -- optional per-launch event timing (sg_trace_*)

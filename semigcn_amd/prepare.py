@@ -13,7 +13,7 @@ Replaces the tail of the reference's preprocess/prepare.py -- everything after t
   ============================  ==========================================================
 
 MeshFix's stage before them is ``semigcn_amd.components`` / ``holes`` / ``repair``; the isotropic remesh between the two is
-``semigcn_amd.remesh`` (splits, flips, relaxation and re-projection; edge collapse stays out of scope).  The reference does the mask and the smoothing with pymeshlab filters and the scaling with numpy over a ``Mesh`` object; here the mask is the closest-point
+``semigcn_amd.remesh`` (splits, collapses, flips, relaxation and re-projection).  The reference does the mask and the smoothing with pymeshlab filters and the scaling with numpy over a ``Mesh`` object; here the mask is the closest-point
 query of ``evaluate.Surface`` (csrc/mesh_dist.hip) and the other two are csrc/mesh_smooth.hip.  HIP device only, like
 the rest of the package: a CPU tensor raises ``SemigcnLibraryError``.
 

@@ -1,12 +1,14 @@
-"""Refine a mesh to a target edge length on the device: split long edges, flip towards regular valence, relax and re-project.
+"""Refine a mesh to a target edge length on the device: split long edges, collapse short ones, flip towards regular
+valence, relax and re-project.
 
-Replaces, apart from edge collapse, the isotropic remesh the reference runs between MeshFix and the scaling
-(preprocess/prepare.py:35-42: MeshLab's ``remeshing_isotropic_explicit_remeshing`` at 0.6 % of the box diagonal).  What
-the networks need from that step is a uniform edge length and valences near 6; ``holes.fill_holes`` patches at roughly
-the border's edge length, a ``-CAD`` input arrives with a few huge triangles, and ``meshprep.qem_contract`` only coarsens.
-**Edge collapse is not done here**: short edges stay and are only counted (``n_short``).  MeshLab is not available to
-compare against; the construction below is this module's own and is the specification the tests pin
-(tests/remesh_oracle.py restates it in numpy with serial, dictionary-based code).  The kernels are csrc/mesh_remesh.hip.
+Replaces the isotropic remesh the reference runs between MeshFix and the scaling (preprocess/prepare.py:35-42: MeshLab's
+``remeshing_isotropic_explicit_remeshing`` at 0.6 % of the box diagonal).  What the networks need from that step is a
+uniform edge length and valences near 6; ``holes.fill_holes`` patches at roughly the border's edge length, a ``-CAD``
+input arrives with a few huge triangles, and ``meshprep.qem_contract`` only coarsens.  Edge collapse is its own operation
+(2a.) and ``refine_mesh`` runs it only when asked (``collapse=True``); without it short edges stay and are only counted
+(``n_short``).  MeshLab is not available to compare against; the construction below is this module's own and is the
+specification the tests pin (tests/remesh_oracle.py and tests/collapse_oracle.py restate it in numpy with serial,
+dictionary-based code).  The kernels are csrc/mesh_remesh.hip.
 
 **Input.**  ``(vs float32 [V, 3], faces int64 [F, 3])``, as ``repair.repair`` returns it.  Every undirected edge must have
 one face (a border edge) or two faces that run it in opposite directions.  ``ValueError`` is raised -- and nothing is done --
@@ -35,6 +37,39 @@ integers, so the hashes of two edges never tie; it breaks the long tie chains of
   along the surface (a regular grid under a smooth stretch, without noise) the rounds follow that slope one face at a time
   and their number grows with its length; scans and jittered meshes break such chains after a few faces.  ``parents`` is ``(i, i)`` for a vertex of the input; the ends of an inserted vertex may be inserted ones.
 
+**2a. collapse_short_edges.**  A round works on the mesh it starts with: edge table, ranks, ``val``, border flags and
+positions.  ``ring(v)`` is the set of vertices that share an edge with ``v``.
+
+* ``lo2 = float32((4/5 target)^2)`` and ``thr2 = float32((4/3 target)^2)``, each formed once on the host in float64
+  (``collapse_threshold``, ``split_threshold``).  An edge is *short* when ``len2 < lo2``, ``len2`` as in 1.
+* A short edge ``{a, b}`` with two faces is a *candidate* when all of the following holds.  At most one end is a border
+  vertex.  The kept vertex ``k`` is the border end when there is one, ``min(a, b)`` otherwise (vertices of the input
+  outlive inserted ones); the removed vertex ``r`` is the other end, so ``r`` is interior and the faces at ``r`` form a
+  fan; that fan must be one closed cycle (a vertex at which two fans touch is never removed).  With ``c`` the third vertex of
+  the face of the lower half-edge and ``d`` that of the other face, ``c != d``.  *Link:* among ``ring(r) - {k}`` exactly
+  two vertices ``w`` have ``{k, w}`` as an edge of the round's mesh (necessarily ``c`` and ``d``).  *Valence floors:*
+  ``val[c] - 1``, ``val[d] - 1`` and ``val[k] + val[r] - 4`` each stay at or above 3 (2 for a border vertex), which refuses
+  the tetrahedron.  *Length guard:* for every ``w`` in ``ring(r) - {k}``, not ``len2(k, w) > thr2``: a collapse never
+  creates an edge that 1. would split, so the two stages cannot feed each other and ``n_long == 0`` keeps its exact
+  meaning.  *Fold-over guard:* every face at ``r`` that does not contain ``k``, rotated to read ``(r, x, y)``, has
+  ``n(r, x, y) . n(k, x, y) > 0`` strictly, with ``n``, the cross and the dot product of the flip guard (2.), in float64.
+* The priority is (``0xFFFFFFFF - bits(len2)``, ``hash(rank)``, lower rank): the shortest edge comes first; packed as
+  ``key << 32 | hash`` as in 2.  The hash is a bijection, so two candidates never tie.
+* The *footprint* of a candidate is ``{r} + ring(r)``; it contains ``k``, ``c`` and ``d``.  A candidate is *selected* when no
+  candidate whose footprint meets its own has a higher priority.  A collapse reads and writes only inside its own
+  footprint: it rewrites the faces at ``r`` (all their vertices are in the footprint), creates the edges ``{k, w}`` for ``w``
+  in ``ring(r)``, and changes the valences of ``k``, ``c`` and ``d``.  Footprint-disjoint winners are therefore independent,
+  and the round's analysis stays valid for all of them.  The best candidate of the mesh always wins, so a round with a
+  candidate makes progress.
+* Apply: the two faces of the edge are deleted; every other face at ``r`` gets ``k`` in place of ``r`` in the same slot
+  (orientation is preserved); vertex ``r`` is deleted; no position changes.  Surviving vertices and faces keep their relative
+  order (stable compaction).  The border flags are carried over: a collapse here cannot change which vertices lie on a
+  border.  ``parents`` entries are renumbered, and an entry that named a removed vertex names the vertex it went into.
+* Rounds repeat until none is selected or ``max_rounds`` rounds ran (default 128); running out of rounds is reported, not
+  raised.  ``counts`` holds the collapses per round, ``n_short`` the short edges of the result, whether or not a guard
+  blocked them.  ``vertex_ids[i]`` is the input index of vertex ``i`` of the result (``vs == input[vertex_ids]``, bit for
+  bit); ``merged_into[j]`` is the index in the result of the vertex that input vertex ``j`` ended up in.
+
 **2. flip_edges.**  ``val[v]`` is the number of distinct edges at ``v``; the target valence is 6, or 4 for a vertex on a
 border edge.  The *deviation* is the sum of ``|val - target|`` over the vertices that have an edge.
 
@@ -55,7 +90,10 @@ border edge.  The *deviation* is the sum of ``|val - target|`` over the vertices
 ``evaluate.Surface.query`` on the moved vertices: the closest points become the positions.  Border vertices never move.
 
 **4. refine_mesh.**  ``target`` defaults to ``target_percent`` % of the input's box diagonal (MeshLab's ``Percentage``).
-The ``Surface`` is built once, from the input.  Each iteration is split (all rounds) -> flip -> relax_project.  Since
+The ``Surface`` is built once, from the input.  Each iteration is split (all rounds) -> flip -> relax_project, or with
+``collapse=True`` split -> collapse -> flip -> relax_project on one plan: the splits that repair long edges leave slivers,
+the collapse removes them before the flips see the valences.  A collapse renumbers the vertices, so ``Refined.parents`` is
+``None`` then.  The closing passes are the same either way: a collapse creates no long edge, and they never collapse.  Since
 relax_project moves vertices, it can push an edge back over 4/3 target; after the last iteration up to ``CLOSING_PASSES``
 closing passes therefore split again (all rounds) and project only the vertices they insert (border ones stay), until a
 pass finds no long edge: ``n_long == 0`` in the report then means that no edge of the RESULT has ``len2 > thr2``, exactly.
@@ -68,12 +106,14 @@ Inputs are what ``evaluate`` accepts; HIP device only: a CPU tensor raises ``Sem
 
 Command line::
 
-    python -m semigcn_amd.remesh in.obj out.obj [--target X | --target-percent P] [--iterations N]
+    python -m semigcn_amd.remesh in.obj out.obj [--target X | --target-percent P] [--iterations N] [--collapse]
     python -m semigcn_amd.remesh --torus NU NV --stretch S [--repeat R] [--target X | --target-percent P] [--iterations N]
+                                 [--collapse]
 
 prints one JSON line with the sizes before and after, the rounds, the report and the device time of each stage
 (``surface_ms``, ``split_ms``, ``flip_ms``, ``relax_ms`` and ``report_ms``, summed over the iterations).  ``--torus NU NV --stretch S`` runs on
-``synth.torus_mesh(NU, NV)`` with x scaled by S.
+``synth.torus_mesh(NU, NV)`` with x scaled by S.  ``--collapse`` runs the collapse stage in every iteration and adds
+``n_collapsed``, ``collapse_rounds`` and ``collapse_ms``.
 """
 from __future__ import annotations
 
@@ -91,8 +131,8 @@ from . import capi, prepare
 from .capi import RemeshPlan, SemigcnLibraryError
 from .evaluate import Surface, _vs_faces, read_obj
 
-__all__ = ["split_long_edges", "flip_edges", "relax_project", "refine_mesh", "Split", "Flipped", "Refined", "RemeshPlan",
-           "split_threshold", "CLOSING_PASSES"]
+__all__ = ["split_long_edges", "collapse_short_edges", "flip_edges", "relax_project", "refine_mesh", "Split", "Collapsed",
+           "Flipped", "Refined", "RemeshPlan", "split_threshold", "collapse_threshold", "CLOSING_PASSES"]
 
 #: refine_mesh: at most this many closing passes (split, project the inserted vertices) after the last iteration
 CLOSING_PASSES = 4
@@ -109,6 +149,17 @@ class Split:
 
 
 @dataclass
+class Collapsed:
+    """What ``collapse_short_edges`` returns.  ``vs == input[vertex_ids]``, bit for bit."""
+    vs: torch.Tensor            # float32 [V', 3]
+    faces: torch.Tensor         # int64 [F', 3]
+    vertex_ids: torch.Tensor    # int64 [V']: the input index of every vertex of the result
+    merged_into: torch.Tensor   # int64 [V]: the index in the result of the vertex every input vertex ended up in
+    counts: List[int]           # collapses per round
+    n_short: int                # short edges left, whether or not a guard blocked them
+
+
+@dataclass
 class Flipped:
     """What ``flip_edges`` returns; the positions are untouched."""
     faces: torch.Tensor         # int64 [F, 3]
@@ -122,7 +173,8 @@ class Refined:
     """What ``refine_mesh`` returns."""
     vs: torch.Tensor            # float32 [V', 3]
     faces: torch.Tensor         # int64 [F', 3]
-    parents: torch.Tensor       # int64 [V', 2]: (i, i) for a vertex of the input, the ends of the split edge otherwise
+    parents: Optional[torch.Tensor]   # int64 [V', 2]: (i, i) for a vertex of the input, the ends of the split edge otherwise;
+                                      # None with collapse=True: a collapse renumbers the vertices
     report: dict
     stage_ms: Optional[dict] = None
 
@@ -130,6 +182,11 @@ class Refined:
 def split_threshold(target: float) -> float:
     """``thr2 = float32((4/3 target)^2)``, formed in float64."""
     return float(np.float32((4.0 / 3.0 * float(target)) ** 2))
+
+
+def collapse_threshold(target: float) -> float:
+    """``lo2 = float32((4/5 target)^2)``, formed in float64."""
+    return float(np.float32((4.0 / 5.0 * float(target)) ** 2))
 
 
 def _check_target(target, what="target"):
@@ -195,6 +252,23 @@ def split_long_edges(vs, faces, target: float, max_rounds: int = 64) -> Split:
     return Split(out_vs, out_faces, parents, counts, n_long)
 
 
+def collapse_short_edges(vs, faces, target: float, max_rounds: int = 128) -> Collapsed:
+    """Collapse the interior edges shorter than 4/5 ``target`` that the guards allow (module docstring, 2a.)."""
+    target, max_rounds = _check_target(target), _check_rounds(max_rounds, "max_rounds")
+    _check_mesh((vs, faces))
+    vs, faces = _vs_faces(vs, faces)
+    with capi._on_device(vs.device):
+        plan = _plan(vs, faces)
+        try:
+            counts, n_short = plan.collapse(collapse_threshold(target), split_threshold(target), max_rounds)
+            out_vs, out_faces, _, _ = plan.export()
+            vertex_ids, merged_into = plan.collapse_maps()
+        finally:
+            torch.cuda.current_stream(vs.device).synchronize()     # the plan's buffers are freed with it
+            plan.close()
+    return Collapsed(out_vs, out_faces, vertex_ids, merged_into, counts, n_short)
+
+
 def flip_edges(vs, faces, max_rounds: int = 32) -> Flipped:
     """Flip edges towards valence 6 (4 on the border) (module docstring, 2.)."""
     max_rounds = _check_rounds(max_rounds, "max_rounds")
@@ -253,13 +327,18 @@ def _edge_report(vs, faces, target: float) -> dict:
 
 
 def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.6, iterations: int = 5,
-                split_rounds: int = 64, flip_rounds: int = 32, relax_steps: int = 1, timings: bool = False) -> Refined:
+                split_rounds: int = 64, flip_rounds: int = 32, relax_steps: int = 1, timings: bool = False,
+                collapse: bool = False, collapse_rounds: int = 128) -> Refined:
     """Refine ``mesh`` to the edge length ``target`` (default: ``target_percent`` % of the box diagonal) by ``iterations``
     of split -> flip -> relax_project against the input's surface (module docstring, 4.).  ``timings``: also measure the
-    device time of the stages (``Refined.stage_ms``; one more synchronisation)."""
+    device time of the stages (``Refined.stage_ms``; one more synchronisation).  ``collapse``: every iteration is
+    split -> collapse -> flip -> relax_project (at most ``collapse_rounds`` rounds of 2a.); the vertices are renumbered, so
+    ``Refined.parents`` is ``None``, and every iteration's report entry gains ``"collapse"`` and
+    ``"n_short_after_collapse"``."""
     from .holes import _Stages
     iterations = _check_rounds(iterations, "iterations")
     split_rounds, flip_rounds = _check_rounds(split_rounds, "split_rounds"), _check_rounds(flip_rounds, "flip_rounds")
+    collapse_rounds = _check_rounds(collapse_rounds, "collapse_rounds")
     relax_steps = _check_rounds(relax_steps, "relax_steps")
     if target is not None:
         target = _check_target(target)
@@ -274,7 +353,7 @@ def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.
                 raise ValueError("refine_mesh: an empty mesh has no box diagonal; give target")
             diag = float((vs.max(0).values.double() - vs.min(0).values.double()).norm())
             target = _check_target(target_percent / 100.0 * diag, "target (target_percent of the box diagonal)")
-        thr2 = split_threshold(target)
+        thr2, lo2 = split_threshold(target), collapse_threshold(target)
         _plan(vs, faces).close()                                  # refuse an invalid input before anything is built
         ms = {}
 
@@ -298,18 +377,24 @@ def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.
                         st.mark("report")
                     counts, n_long = plan.split(thr2, split_rounds)
                     st.mark("split")
+                    if collapse:
+                        collapsed, n_short = plan.collapse(lo2, thr2, collapse_rounds)
+                        st.mark("collapse")
                     flips, before, after = plan.flip(flip_rounds)
                     vs, faces, par, border = plan.export()
                     st.mark("flip")
                 finally:
                     torch.cuda.current_stream(vs.device).synchronize()
                     plan.close()
-                parents = torch.cat([parents, par[parents.shape[0]:]])
+                if not collapse:
+                    parents = torch.cat([parents, par[parents.shape[0]:]])
                 vs = _relax_project(vs, faces, border, surf, relax_steps)
                 st.mark("relax")
                 add(st)
                 rounds.append({"split": counts, "flip": flips, "n_long": n_long, "deviation_after_split": before,
                                "deviation_after_flip": after})
+                if collapse:
+                    rounds[-1].update({"collapse": collapsed, "n_short_after_collapse": n_short})
             # closing: relax_project can push an edge back over the threshold.  Split again (all rounds), project only what
             # was inserted, and repeat until a pass finds nothing to split: then no position changed after the last analysis,
             # so n_long == 0 in the report means that no edge of the RESULT has len2 > thr2, exactly.
@@ -329,7 +414,8 @@ def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.
                     torch.cuda.current_stream(vs.device).synchronize()
                     plan.close()
                 closing.append(sum(counts))
-                parents = torch.cat([parents, par[n_before:]])
+                if not collapse:
+                    parents = torch.cat([parents, par[n_before:]])
                 closest = surf.query(vs[n_before:], signed=False)[2]
                 vs[n_before:] = torch.where(border[n_before:, None], vs[n_before:], closest)
             st.mark("split")
@@ -342,14 +428,14 @@ def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.
         report.update(_edge_report(vs, faces, target))
         st.mark("report")
         add(st)
-    return Refined(vs, faces, parents, report, ms if timings else None)
+    return Refined(vs, faces, None if collapse else parents, report, ms if timings else None)
 
 
 def main(argv=None) -> int:
     from . import synth
     ap = argparse.ArgumentParser(prog="python -m semigcn_amd.remesh",
-                                 description="refine a triangle mesh to a target edge length: split, flip, relax and project "
-                                             "(the isotropic remesh of preprocess/prepare.py without edge collapse)")
+                                 description="refine a triangle mesh to a target edge length: split, collapse (--collapse), flip, "
+                                             "relax and project (the isotropic remesh of preprocess/prepare.py)")
     ap.add_argument("input", nargs="?", help="the mesh to refine (OBJ)")
     ap.add_argument("output", nargs="?", help="where the refined mesh goes (OBJ)")
     ap.add_argument("--target", type=float, default=None, help="target edge length")
@@ -357,6 +443,7 @@ def main(argv=None) -> int:
     ap.add_argument("--iterations", type=int, default=5)
     ap.add_argument("--torus", type=int, nargs=2, metavar=("NU", "NV"), help="run on a synthetic torus instead of an OBJ")
     ap.add_argument("--stretch", type=float, default=1.0, help="with --torus: scale x by this factor")
+    ap.add_argument("--collapse", action="store_true", help="collapse short edges between the splits and the flips")
     ap.add_argument("--repeat", type=int, default=1, help="run this many times and report the last (the first ones warm up)")
     args = ap.parse_args(argv)
     if (args.input is None) == (args.torus is None):
@@ -371,7 +458,8 @@ def main(argv=None) -> int:
         m = synth.torus_mesh(args.torus[0], args.torus[1], masks=False)
         mesh = ((m.vs * np.array([args.stretch, 1.0, 1.0])).astype(np.float32), m.faces)
     for _ in range(args.repeat):
-        out = refine_mesh(mesh, target=args.target, target_percent=args.target_percent, iterations=args.iterations, timings=True)
+        out = refine_mesh(mesh, target=args.target, target_percent=args.target_percent, iterations=args.iterations, timings=True,
+                          collapse=args.collapse)
     if args.output:
         prepare.write_obj(args.output, out.vs, out.faces)
     nv, nf = (int(x.shape[0]) for x in _vs_faces(mesh))
@@ -381,6 +469,8 @@ def main(argv=None) -> int:
     rec = {"n_vertices_in": nv, "n_faces_in": nf, "split_rounds": [len(i["split"]) for i in its],
            "flip_rounds": [len(i["flip"]) for i in its], "n_split": [sum(i["split"]) for i in its],
            "n_flipped": [sum(i["flip"]) for i in its]}
+    if args.collapse:
+        rec.update({"n_collapsed": [sum(i["collapse"]) for i in its], "collapse_rounds": [len(i["collapse"]) for i in its]})
     rec.update(rep)
     rec.update({k: round(v, 4) for k, v in out.stage_ms.items()})
     rec["total_ms"] = round(sum(out.stage_ms.values()), 4)
