@@ -1296,16 +1296,58 @@ def face_mask_bits(faces: torch.Tensor, vbits: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _faces_arg(faces: torch.Tensor) -> torch.Tensor:
+    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise SemigcnLibraryError(f"faces must be int64 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+    return faces.contiguous()
+
+
+def _vs_arg(vs: torch.Tensor, plan=None) -> torch.Tensor:
+    """``vs`` float32 [V, 3]; with ``plan``: exactly [plan.num_vertices, 3], on the plan's device."""
+    if plan is None:
+        if vs.dtype != torch.float32 or vs.dim() != 2 or vs.shape[1] != 3:
+            raise SemigcnLibraryError(f"vs must be float32 [V, 3], got {vs.dtype} {tuple(vs.shape)}")
+    else:
+        if vs.dtype != torch.float32 or tuple(vs.shape) != (plan.num_vertices, 3):
+            raise SemigcnLibraryError(f"vs must be float32 [{plan.num_vertices}, 3], got {vs.dtype} {tuple(vs.shape)}")
+        if vs.device != plan.device:
+            raise SemigcnLibraryError(f"vs on {vs.device}, plan on {plan.device}")
+    return vs
+
+
 class _OwnedHandle:
-    """What the classes that own one mesh object of the library share: the handle ``_h``, the entry point that destroys
-    it, and closing it once -- by ``close()`` or when the object goes."""
+    """What the classes that own one mesh object of the library share: the handle ``_h``, the entry points that create,
+    query and destroy it, and closing it once -- by ``close()`` or when the object goes.  As a context manager it waits for
+    the current stream of its device and then closes: the object's buffers are freed with it, and a kernel that was
+    launched inside the block may still read them."""
 
     _h = None
     _destroy = ""          # name of the sg_*_destroy entry point
+    _query_fn, _query_len = "", 0          # the sg_*_query entry point and the number of int64 it fills
+
+    def _create(self, entry_point: str, device: torch.device, *args):
+        """``sg_*_create(*args, &handle)`` on ``device``.  ``_h`` is null until that succeeded, for ``close()``."""
+        self._h = c_void_p(0)
+        out = c_void_p()
+        with _on_device(device):
+            _check(getattr(load(), entry_point)(*args, byref(out)), entry_point)
+        self._h = out
+
+    def _query(self):
+        info = (c_int64 * self._query_len)()
+        _check(getattr(load(), self._query_fn)(self._h, info), self._query_fn)
+        return list(info)
 
     def _open(self):
         if not self._h.value:
             raise SemigcnLibraryError(f"{type(self).__name__} is closed")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        torch.cuda.current_stream(self.device).synchronize()
+        self.close()
 
     def close(self):
         if self._h is not None and self._h.value:
@@ -1328,18 +1370,9 @@ class SurfaceHandle(_OwnedHandle):
     def __init__(self, vs: torch.Tensor, faces: torch.Tensor):
         _require_device(vs, "vs")
         _require_device(faces, "faces")
-        if vs.dtype != torch.float32 or vs.dim() != 2 or vs.shape[1] != 3:
-            raise SemigcnLibraryError(f"vs must be float32 [V, 3], got {vs.dtype} {tuple(vs.shape)}")
-        if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-            raise SemigcnLibraryError(f"faces must be int64 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
-        vs, faces = vs.contiguous(), faces.contiguous()
+        vs, faces = _vs_arg(vs).contiguous(), _faces_arg(faces)
         self.device, self.num_vertices, self.num_faces = vs.device, vs.shape[0], faces.shape[0]
-        self._h = c_void_p(0)
-        out = c_void_p()
-        with _on_device(vs.device):
-            _check(load().sg_surface_create(_ptr(vs), vs.shape[0], _ptr(faces), faces.shape[0], _stream(vs), byref(out)),
-                   "sg_surface_create")
-        self._h = out
+        self._create("sg_surface_create", vs.device, _ptr(vs), vs.shape[0], _ptr(faces), faces.shape[0], _stream(vs))
 
     def query(self, pts: torch.Tensor, signed: bool = True, with_closest: bool = True):
         """(dist float32 [N], face int32 [N], closest float32 [N, 3] or None) for the points pts float32 [N, 3]."""
@@ -1348,6 +1381,7 @@ class SurfaceHandle(_OwnedHandle):
             raise SemigcnLibraryError(f"points must be float32 [N, 3], got {pts.dtype} {tuple(pts.shape)}")
         if pts.device != self.device:
             raise SemigcnLibraryError(f"points on {pts.device}, surface on {self.device}")
+        self._open()
         pts = pts.contiguous()
         N = pts.shape[0]
         dist = torch.empty(N, dtype=torch.float32, device=pts.device)
@@ -1369,6 +1403,7 @@ class SurfaceHandle(_OwnedHandle):
         if faces.dtype != torch.int64 or tuple(faces.shape) != (self.num_faces, 3) or not faces.is_contiguous():
             raise SemigcnLibraryError(f"faces must be the contiguous int64 [{self.num_faces}, 3] the surface was built from, "
                                       f"got {faces.dtype} {tuple(faces.shape)}")
+        self._open()
 
     def self_count(self, vs: torch.Tensor, faces: torch.Tensor):
         """(n_any int32 [F], n_upper int32 [F], stats int64 [2] = degenerate faces, dropped subtrees) of
@@ -1453,16 +1488,9 @@ class SmoothPlan(_OwnedHandle):
 
     def __init__(self, faces: torch.Tensor, num_vertices: int):
         _require_device(faces, "faces")
-        if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-            raise SemigcnLibraryError(f"faces must be int64 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
-        faces = faces.contiguous()
+        faces = _faces_arg(faces)
         self.device, self.num_vertices, self.num_faces = faces.device, int(num_vertices), faces.shape[0]
-        self._h = c_void_p(0)
-        out = c_void_p()
-        with _on_device(faces.device):
-            _check(load().sg_smooth_create(_ptr(faces), faces.shape[0], self.num_vertices, _stream(faces), byref(out)),
-                   "sg_smooth_create")
-        self._h = out
+        self._create("sg_smooth_create", faces.device, _ptr(faces), faces.shape[0], self.num_vertices, _stream(faces))
 
     def run(self, vs: torch.Tensor, steps: int = 30, movable: Optional[torch.Tensor] = None) -> torch.Tensor:
         """float32 [V, 3]: ``steps`` Jacobi steps from ``vs``; ``movable`` bool [V] (False = the vertex stays)."""
@@ -1470,10 +1498,7 @@ class SmoothPlan(_OwnedHandle):
         if steps < 0:
             raise ValueError(f"steps must be >= 0, got {steps}")
         _require_device(vs, "vs")
-        if vs.dtype != torch.float32 or tuple(vs.shape) != (self.num_vertices, 3):
-            raise SemigcnLibraryError(f"vs must be float32 [{self.num_vertices}, 3], got {vs.dtype} {tuple(vs.shape)}")
-        if vs.device != self.device:
-            raise SemigcnLibraryError(f"vs on {vs.device}, plan on {self.device}")
+        _vs_arg(vs, self)
         self._open()
         if movable is not None:
             _require_device(movable, "movable")
@@ -1494,27 +1519,16 @@ class FillPlan(_OwnedHandle):
     ``bad_vertex`` say why a boundary cannot be ordered; ``loops`` / ``plan`` / ``emit`` then raise."""
 
     _destroy = "sg_fill_destroy"
+    _query_fn, _query_len = "sg_fill_query", 8
 
     def __init__(self, faces: torch.Tensor, num_vertices: int):
         _require_device(faces, "faces")
-        if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-            raise SemigcnLibraryError(f"faces must be int64 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
-        faces = faces.contiguous()
+        faces = _faces_arg(faces)
         self.device, self.num_vertices, self.num_faces = faces.device, int(num_vertices), faces.shape[0]
-        self._h = c_void_p(0)
-        out = c_void_p()
-        with _on_device(faces.device):
-            _check(load().sg_fill_create(_ptr(faces), faces.shape[0], self.num_vertices, _stream(faces), byref(out)),
-                   "sg_fill_create")
-        self._h = out
+        self._create("sg_fill_create", faces.device, _ptr(faces), faces.shape[0], self.num_vertices, _stream(faces))
         info = self._query()
         self.num_loops, self.num_boundary, self.n_repeated, self.n_bowtie, self.bad_vertex = (int(v) for v in info[:5])
         self.num_new_vertices = self.num_new_faces = None
-
-    def _query(self):
-        info = (c_int64 * 8)()
-        _check(load().sg_fill_query(self._h, info), "sg_fill_query")
-        return list(info)
 
     @property
     def orderable(self) -> bool:
@@ -1549,8 +1563,7 @@ class FillPlan(_OwnedHandle):
             _require_device(t, name)
             if t.device != self.device or not t.is_contiguous():
                 raise SemigcnLibraryError(f"{name}: a contiguous tensor on {self.device}")
-        if vs.dtype != torch.float32 or tuple(vs.shape) != (self.num_vertices, 3):
-            raise SemigcnLibraryError(f"vs must be float32 [{self.num_vertices}, 3], got {vs.dtype} {tuple(vs.shape)}")
+        _vs_arg(vs, self)
         if new_vs.dtype != torch.float32 or tuple(new_vs.shape) != (self.num_new_vertices, 3):
             raise SemigcnLibraryError(f"new_vs must be float32 [{self.num_new_vertices}, 3], got {new_vs.dtype} {tuple(new_vs.shape)}")
         if new_faces.dtype != torch.int64 or tuple(new_faces.shape) != (self.num_new_faces, 3):
@@ -1569,6 +1582,7 @@ class PartsPlan(_OwnedHandle):
     compacted mesh of the last ``select``; ``select`` may be called again with another ``keep``."""
 
     _destroy = "sg_parts_destroy"
+    _query_fn, _query_len = "sg_parts_query", 8
 
     CONNECTIVITY = {"edge": 0, "vertex": 1}
 
@@ -1576,25 +1590,14 @@ class PartsPlan(_OwnedHandle):
         if connectivity not in self.CONNECTIVITY:
             raise ValueError(f"connectivity must be 'edge' or 'vertex', got {connectivity!r}")
         _require_device(faces, "faces")
-        if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-            raise SemigcnLibraryError(f"faces must be int64 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
-        faces = faces.contiguous()
+        faces = _faces_arg(faces)
         self.device, self.num_vertices, self.num_faces = faces.device, int(num_vertices), faces.shape[0]
         self.connectivity = connectivity
-        self._h = c_void_p(0)
-        out = c_void_p()
-        with _on_device(faces.device):
-            _check(load().sg_parts_create(_ptr(faces), faces.shape[0], self.num_vertices, self.CONNECTIVITY[connectivity],
-                                          _stream(faces), byref(out)), "sg_parts_create")
-        self._h = out
+        self._create("sg_parts_create", faces.device, _ptr(faces), faces.shape[0], self.num_vertices,
+                     self.CONNECTIVITY[connectivity], _stream(faces))
         info = self._query()
         self.num_components, _, _, self.n_degenerate, self.largest, self.largest_faces = (int(v) for v in info[:6])
         self.num_kept_vertices = self.num_kept_faces = None
-
-    def _query(self):
-        info = (c_int64 * 8)()
-        _check(load().sg_parts_query(self._h, info), "sg_parts_query")
-        return list(info)
 
     def labels(self):
         """(face_label int64 [F], -1 = degenerate; face_count int64 [K]) on the plan's device."""
@@ -1627,10 +1630,7 @@ class PartsPlan(_OwnedHandle):
         if self.num_kept_vertices is None:
             raise SemigcnLibraryError("PartsPlan.emit: call select() first")
         _require_device(vs, "vs")
-        if vs.dtype != torch.float32 or tuple(vs.shape) != (self.num_vertices, 3):
-            raise SemigcnLibraryError(f"vs must be float32 [{self.num_vertices}, 3], got {vs.dtype} {tuple(vs.shape)}")
-        if vs.device != self.device:
-            raise SemigcnLibraryError(f"vs on {vs.device}, plan on {self.device}")
+        _vs_arg(vs, self)
         vs = vs.detach().contiguous()
         nv, nf = self.num_kept_vertices, self.num_kept_faces
         new_vs = torch.empty((nv, 3), dtype=torch.float32, device=self.device)
@@ -1651,36 +1651,23 @@ class RemeshPlan(_OwnedHandle):
     ``split``, ``collapse`` and ``flip`` then raise."""
 
     _destroy = "sg_remesh_destroy"
+    _query_fn, _query_len = "sg_remesh_query", 16
     _map_sizes = None                     # (V', V_before) of the last collapse call
 
     def __init__(self, vs: torch.Tensor, faces: torch.Tensor):
         _require_device(vs, "vs")
         _require_device(faces, "faces")
-        if vs.dtype != torch.float32 or vs.dim() != 2 or vs.shape[1] != 3:
-            raise SemigcnLibraryError(f"vs must be float32 [V, 3], got {vs.dtype} {tuple(vs.shape)}")
-        if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3:
-            raise SemigcnLibraryError(f"faces must be int64 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+        vs, faces = _vs_arg(vs).detach().contiguous(), _faces_arg(faces)
         if faces.device != vs.device:
             raise SemigcnLibraryError(f"faces on {faces.device}, vs on {vs.device}")
-        vs, faces = vs.detach().contiguous(), faces.contiguous()
         self.device = vs.device
-        self._h = c_void_p(0)
-        out = c_void_p()
-        with _on_device(self.device):
-            _check(load().sg_remesh_create(_ptr(vs), vs.shape[0], _ptr(faces), faces.shape[0], _stream(vs), byref(out)),
-                   "sg_remesh_create")
-        self._h = out
+        self._create("sg_remesh_create", self.device, _ptr(vs), vs.shape[0], _ptr(faces), faces.shape[0], _stream(vs))
         info = self._query()
         (self.num_vertices, self.num_faces, self.num_edges, self.num_border_edges, self.n_nonmanifold, self.n_misoriented,
          self.n_degenerate, self.n_nonfinite) = (int(v) for v in info[:8])
         self.bad_edge = (int(info[8]), int(info[9]))
         self.bad_face, self.bad_vertex = int(info[10]), int(info[11])
         self.valid = bool(info[14])
-
-    def _query(self):
-        info = (c_int64 * 16)()
-        _check(load().sg_remesh_query(self._h, info), "sg_remesh_query")
-        return list(info)
 
     def _sizes(self):
         self.num_vertices, self.num_faces = (int(v) for v in self._query()[:2])

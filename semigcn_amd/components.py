@@ -53,7 +53,7 @@ import torch
 
 from . import capi
 from .capi import PartsPlan, SemigcnLibraryError
-from .evaluate import _device_tensor, _vs_faces, read_obj
+from .mesh_common import Stages, device_tensor, read_obj, vs_faces, write_obj
 
 __all__ = ["face_components", "keep_components", "Components", "Kept", "PartsPlan"]
 
@@ -97,14 +97,9 @@ def _components_of(plan: PartsPlan) -> Components:
 def face_components(faces, num_vertices: int, connectivity: str = "edge") -> Components:
     """The connected components of the triangle list ``faces`` [F, 3] over ``num_vertices`` vertices."""
     _check_connectivity(connectivity)
-    f = _device_tensor(faces, torch.int64, "faces").reshape(-1, 3)
-    with capi._on_device(f.device):
-        plan = PartsPlan(f, int(num_vertices), connectivity)
-        try:
-            return _components_of(plan)
-        finally:
-            torch.cuda.current_stream(f.device).synchronize()
-            plan.close()
+    f = device_tensor(faces, torch.int64, "faces").reshape(-1, 3)
+    with capi._on_device(f.device), PartsPlan(f, int(num_vertices), connectivity) as plan:
+        return _components_of(plan)
 
 
 def _keep_mask(keep, comps: Components, min_faces, device) -> torch.Tensor:
@@ -130,7 +125,6 @@ def keep_components(mesh, keep="largest", min_faces: Optional[int] = None, conne
     ``"all"`` or a bool / uint8 tensor or array with one entry per component; ``min_faces``: also drop kept components
     with fewer faces.  ``(Kept.vs, Kept.faces)`` is a valid input to ``holes.fill_holes`` and ``prepare.prepare_inputs``.
     ``timings``: also measure the device time of the stages (``Kept.stage_ms``; one more synchronisation)."""
-    from .holes import _Stages
     _check_connectivity(connectivity)
     if isinstance(keep, str):
         if keep not in ("largest", "all"):
@@ -142,11 +136,10 @@ def keep_components(mesh, keep="largest", min_faces: Optional[int] = None, conne
         raise ValueError(f"keep_components: keep must be bool or uint8, got {keep.dtype}")
     if min_faces is not None and int(min_faces) < 0:
         raise ValueError(f"keep_components: min_faces must be >= 0 or None, got {min_faces}")
-    vs, faces = _vs_faces(mesh)
+    vs, faces = vs_faces(mesh)
     with capi._on_device(vs.device):
-        st = _Stages(vs.device, timings)
-        plan = PartsPlan(faces, vs.shape[0], connectivity)
-        try:
+        st = Stages(vs.device, timings)
+        with PartsPlan(faces, vs.shape[0], connectivity) as plan:
             comps = _components_of(plan)
             st.mark("label")
             mask = _keep_mask(keep, comps, min_faces, vs.device)
@@ -154,9 +147,6 @@ def keep_components(mesh, keep="largest", min_faces: Optional[int] = None, conne
             st.mark("select")
             new_vs, new_faces, vertex_ids, face_ids = plan.emit(vs)
             st.mark("emit")
-        finally:
-            torch.cuda.current_stream(vs.device).synchronize()     # the plan's buffers are freed with it
-            plan.close()
         return Kept(new_vs, new_faces, vertex_ids, face_ids, comps, mask, st.result())
 
 
@@ -177,7 +167,7 @@ def with_fragments(vs: torch.Tensor, faces: torch.Tensor, n_fragments: int):
 
 
 def main(argv=None) -> int:
-    from . import holes, prepare
+    from . import holes
     ap = argparse.ArgumentParser(prog="python -m semigcn_amd.components",
                                  description="keep the main connected component of a triangle mesh (the component "
                                              "selection of MeshFix.repair())")
@@ -206,12 +196,12 @@ def main(argv=None) -> int:
     for _ in range(args.repeat):
         out = keep_components(mesh, keep=args.keep, min_faces=args.min_faces, connectivity=args.connectivity, timings=True)
     if args.out:
-        prepare.write_obj(args.out, out.vs, out.faces)
+        write_obj(args.out, out.vs, out.faces)
     c = out.components
     rec = {"n_vertices": int(mesh[0].shape[0]), "n_faces": int(mesh[1].shape[0]), "n_components": len(c),
            "n_degenerate": c.n_degenerate, "largest_faces": int(c.face_count[c.largest]) if len(c) else 0,
            "kept_vertices": int(out.vs.shape[0]), "kept_faces": int(out.faces.shape[0])}
-    rec.update({k: round(v, 4) for k, v in out.stage_ms.items()})
+    rec.update(Stages.record(out.stage_ms))
     print(json.dumps(rec))
     return 0
 

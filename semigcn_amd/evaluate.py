@@ -28,49 +28,14 @@ import math
 import sys
 from typing import Optional
 
-import numpy as np
 import torch
 
-from . import capi
+from . import capi, mesh_common
 from .capi import SemigcnLibraryError
+from .mesh_common import device_tensor, read_obj, vs_faces
 
 #: check/dist_check.py:36-40: the hole threshold on the unsigned distance gt -> org (meshes scaled to unit mean edge)
 EPS_SIMULATED, EPS_REAL = 0.05, 1.0
-
-
-def _device_tensor(x, dtype: torch.dtype, name: str) -> torch.Tensor:
-    if isinstance(x, torch.Tensor):
-        if not x.is_cuda:
-            raise SemigcnLibraryError(
-                f"{name} is on {x.device}: semigcn_amd.evaluate runs on a HIP device only (there is no CPU path; "
-                "pass a cuda tensor or a numpy array)")
-        return x.detach().to(dtype).contiguous()
-    if not torch.cuda.is_available():
-        raise SemigcnLibraryError(f"{name}: no HIP device to copy the array to (semigcn_amd.evaluate has no CPU path)")
-    return torch.as_tensor(np.ascontiguousarray(np.asarray(x)), dtype=dtype).to(
-        torch.device("cuda", torch.cuda.current_device())).contiguous()
-
-
-def _vs_faces(mesh, faces=None):
-    """(vs float32 [V, 3], faces int64 [F, 3]) on the device from a mesh object or a (vs, faces) pair."""
-    if faces is None:
-        if isinstance(mesh, (tuple, list)) and len(mesh) == 2:
-            mesh, faces = mesh
-        elif hasattr(mesh, "vs") and hasattr(mesh, "faces"):
-            mesh, faces = mesh.vs, mesh.faces
-        else:
-            raise TypeError("expected a mesh with .vs / .faces or a (vs, faces) pair")
-    vs = _device_tensor(mesh, torch.float32, "vs")
-    f = _device_tensor(faces, torch.int64, "faces")
-    if f.device != vs.device:
-        f = f.to(vs.device)
-    return vs.reshape(-1, 3), f.reshape(-1, 3)
-
-
-def _points(x) -> torch.Tensor:
-    if hasattr(x, "vs"):
-        x = x.vs
-    return _device_tensor(x, torch.float32, "points").reshape(-1, 3)
 
 
 class Surface:
@@ -78,7 +43,7 @@ class Surface:
     of point sets against it.  Open and non-manifold surfaces are fine (the reference loads org with manifold=False)."""
 
     def __init__(self, vs, faces=None):
-        self.vs, self.faces = _vs_faces(vs, faces)
+        self.vs, self.faces = vs_faces(vs, faces)
         self._h = capi.SurfaceHandle(self.vs, self.faces)
 
     @property
@@ -90,13 +55,19 @@ class Surface:
         (signed by the face normal when ``signed``), the face the closest point lies on, and that point.  A point with a
         NaN or an infinite coordinate gets ``dist = inf``, ``face = 0x7fffffff`` and a NaN ``closest`` row, and leaves
         the other rows alone: test ``torch.isinf(dist)`` before indexing with ``face``."""
-        pts = _points(points)
+        pts = mesh_common.points(points)
         if pts.device != self.device:
             pts = pts.to(self.device)
         return self._h.query(pts, signed=signed)
 
     def close(self):
         self._h.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self._h.__exit__(*exc)
 
 
 def _surface(x) -> Surface:
@@ -129,7 +100,7 @@ def mesh_distance(gt, org, out, real: bool = False, eps: Optional[float] = None,
             raise ValueError("mesh_distance: org is needed unless hole is given")
         q_org = _surface(org).query(gt_vs, signed=False)[0]
     else:
-        hole = _device_tensor(hole, torch.bool, "hole")
+        hole = device_tensor(hole, torch.bool, "hole")
     q = out_s.query(gt_vs, signed=True)[0]
     q_out = gt_s.query(out_s.vs, signed=True)[0]
     sums, hole_mask = capi.mesh_distance_reduce(q, gt_vs, q_org=q_org, eps=float(eps), hole=hole)
@@ -143,35 +114,11 @@ def mesh_distance(gt, org, out, real: bool = False, eps: Optional[float] = None,
 
 def simple_mesh_distance(gt, out) -> float:
     """``hd_all`` alone, without org (check/dist_check.py:13-33)."""
-    gt_vs = _vs_faces(gt)[0] if isinstance(gt, (tuple, list)) else _points(gt)     # gt's faces are not needed
+    gt_vs = vs_faces(gt)[0] if isinstance(gt, (tuple, list)) else mesh_common.points(gt)     # gt's faces are not needed
     q = _surface(out).query(gt_vs, signed=True)[0]
     sums, _ = capi.mesh_distance_reduce(q, gt_vs, hole=torch.zeros(gt_vs.shape[0], dtype=torch.bool, device=q.device))
     s_all, _, _, diag = sums.tolist()
     return s_all / gt_vs.shape[0] / diag if gt_vs.shape[0] and diag else float("nan")
-
-
-def read_obj(path: str):
-    """(vs float32 [V, 3], faces int64 [F, 3]) in the dialect util/mesh.py:35-58 reads: ``v x y z`` with an optional
-    colour, ``f a b c`` with ``a/b/c`` slash forms and negative (relative) indices; anything but a triangle is an
-    error."""
-    vs, faces = [], []
-    with open(path) as f:
-        for ln, line in enumerate(f, 1):
-            tok = line.split()
-            if not tok:
-                continue
-            if tok[0] == "v":
-                vs.append([float(t) for t in tok[1:4]])
-            elif tok[0] == "f":
-                ids = [int(t.split("/")[0]) for t in tok[1:]]
-                if len(ids) != 3:
-                    raise ValueError(f"{path}:{ln}: face with {len(ids)} vertices (only triangles are read)")
-                faces.append([i - 1 if i >= 0 else len(vs) + i for i in ids])
-    v = np.asarray(vs, dtype=np.float32).reshape(-1, 3)
-    fc = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
-    if fc.size and (fc.min() < 0 or fc.max() >= v.shape[0]):
-        raise ValueError(f"{path}: face index outside [0, {v.shape[0]})")
-    return v, fc
 
 
 def main(argv=None) -> int:

@@ -65,7 +65,7 @@ import torch
 
 from . import capi, prepare
 from .capi import FillPlan, SemigcnLibraryError
-from .evaluate import _device_tensor, _vs_faces, read_obj
+from .mesh_common import Stages, device_tensor, read_obj, vs_faces, write_obj
 
 __all__ = ["boundary_loops", "fill_holes", "BoundaryLoops", "Filled", "FillPlan"]
 
@@ -114,33 +114,9 @@ def boundary_loops(faces, num_vertices: int) -> BoundaryLoops:
     """The boundary loops of the triangle list ``faces`` [F, 3] over ``num_vertices`` vertices.  ``ValueError`` when the
     boundary is unorderable; the message names the number of repeated directed half-edges, the number of vertices with
     more than one outgoing boundary half-edge and the smallest offending vertex."""
-    f = _device_tensor(faces, torch.int64, "faces").reshape(-1, 3)
-    plan = _plan(f, num_vertices)
-    try:
+    f = device_tensor(faces, torch.int64, "faces").reshape(-1, 3)
+    with _plan(f, num_vertices) as plan:
         return _loops_of(plan)
-    finally:
-        torch.cuda.current_stream(f.device).synchronize()
-        plan.close()
-
-
-class _Stages:
-    """Device time of named stages, from events on the current stream."""
-
-    def __init__(self, device, on: bool):
-        self.on, self.device, self.marks = on, device, []
-        self.mark(None)
-
-    def mark(self, name):
-        if self.on:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record(torch.cuda.current_stream(self.device))
-            self.marks.append((name, e))
-
-    def result(self):
-        if not self.on:
-            return None
-        torch.cuda.synchronize(self.device)
-        return {name + "_ms": self.marks[i - 1][1].elapsed_time(e) for i, (name, e) in enumerate(self.marks) if i > 0}
 
 
 def fill_holes(mesh, max_hole_edges: Optional[int] = None, fair_steps: int = prepare.SMOOTH_ITER,
@@ -156,12 +132,11 @@ def fill_holes(mesh, max_hole_edges: Optional[int] = None, fair_steps: int = pre
         raise ValueError(f"fill_holes: fair_steps must be >= 0, got {fair_steps}")
     if max_hole_edges is not None and int(max_hole_edges) < 0:
         raise ValueError(f"fill_holes: max_hole_edges must be >= 0 or None, got {max_hole_edges}")
-    vs, faces = _vs_faces(mesh)
+    vs, faces = vs_faces(mesh)
     V, F = vs.shape[0], faces.shape[0]
     with capi._on_device(vs.device):
-        st = _Stages(vs.device, timings)
-        plan = _plan(faces, V)
-        try:
+        st = Stages(vs.device, timings)
+        with _plan(faces, V) as plan:
             loops = _loops_of(plan)
             st.mark("loops")
             Vn, Fn = plan.plan(max_hole_edges)
@@ -171,9 +146,6 @@ def fill_holes(mesh, max_hole_edges: Optional[int] = None, fair_steps: int = pre
             out_faces[:F].copy_(faces)
             filled = plan.emit(vs, out_vs[V:], out_faces[F:])
             st.mark("emit")
-        finally:
-            torch.cuda.current_stream(vs.device).synchronize()     # the plan's buffers are freed with it
-            plan.close()
         inserted = torch.zeros(V + Vn, dtype=torch.bool, device=vs.device)
         inserted[V:] = True
         if fair_steps > 0 and Vn > 0:
@@ -246,11 +218,11 @@ def main(argv=None) -> int:
     for _ in range(args.repeat):
         out = fill_holes(mesh, max_hole_edges=args.max_hole_edges, fair_steps=args.fair_steps, timings=True)
     if args.out:
-        prepare.write_obj(args.out, out.vs, out.faces)
+        write_obj(args.out, out.vs, out.faces)
     rec = {"n_vertices": out.num_original_vertices, "n_faces": out.num_original_faces, "n_loops": len(out.loops),
            "n_filled": int(out.filled.sum()), "n_inserted_vertices": int(out.vs.shape[0] - out.num_original_vertices),
            "n_inserted_faces": int(out.faces.shape[0] - out.num_original_faces), "fair_steps": args.fair_steps}
-    rec.update({k: round(v, 4) for k, v in out.stage_ms.items()})
+    rec.update(Stages.record(out.stage_ms))
     rec.update(extra)
     print(json.dumps(rec))
     return 0

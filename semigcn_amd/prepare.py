@@ -32,18 +32,19 @@ with ``scale``, ``n_vertices``, ``n_masked`` and ``steps``.
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
-import numpy as np
 import torch
 
 from . import capi, meshprep
 from .capi import SemigcnLibraryError, SmoothPlan
-from .evaluate import Surface, _device_tensor, _points, _vs_faces, read_obj
+from .evaluate import Surface
+from .mesh_common import device_tensor, points, read_obj, vs_faces, write_obj
 from .meshprep import MeshTopology
 
 #: preprocess/prepare.py:12-14
@@ -57,20 +58,20 @@ def mean_edge_length(vs, edges) -> torch.Tensor:
     """``sum ||vs[a] - vs[b]|| / E`` over the UNIQUE edge list ``edges`` int64 [E, 2] (``MeshTopology.edges``) -- what
     ``edge_based_scaling`` divides by (preprocess/prepare.py:48-52) -- as a 0-dim float64 device tensor.  Float32 lengths,
     float64 sums in a fixed order (bit-reproducible); no host synchronisation.  ``E == 0`` gives NaN, the reference's 0 / 0."""
-    return capi.mean_edge_length(_points(vs), _device_tensor(edges, torch.int64, "edges").reshape(-1, 2))
+    return capi.mean_edge_length(points(vs), device_tensor(edges, torch.int64, "edges").reshape(-1, 2))
 
 
 def _plan_for(topology_or_faces, num_vertices: int):
-    """(plan, owned): a SmoothPlan for the argument; ``owned`` when it was made here and is closed after use."""
+    """A context that gives a SmoothPlan for the argument: the caller's own, left open, or one made here and closed."""
     if isinstance(topology_or_faces, SmoothPlan):
-        return topology_or_faces, False
+        return contextlib.nullcontext(topology_or_faces)
     if isinstance(topology_or_faces, MeshTopology):
         faces = topology_or_faces.faces
         if topology_or_faces.num_vertices != num_vertices:
             raise SemigcnLibraryError(f"topology of {topology_or_faces.num_vertices} vertices, vs has {num_vertices}")
     else:
-        faces = _device_tensor(topology_or_faces, torch.int64, "faces").reshape(-1, 3)
-    return SmoothPlan(faces, num_vertices), True
+        faces = device_tensor(topology_or_faces, torch.int64, "faces").reshape(-1, 3)
+    return SmoothPlan(faces, num_vertices)
 
 
 def laplacian_smooth(vs, topology_or_faces, steps: int = SMOOTH_ITER, movable=None) -> torch.Tensor:
@@ -98,23 +99,18 @@ def laplacian_smooth(vs, topology_or_faces, steps: int = SMOOTH_ITER, movable=No
     steps = int(steps)
     if steps < 0:
         raise ValueError(f"laplacian_smooth: steps must be >= 0, got {steps}")
-    p = _points(vs)
+    p = points(vs)
     if movable is not None:
-        movable = _device_tensor(movable, torch.bool, "movable")
-    plan, owned = _plan_for(topology_or_faces, p.shape[0])
-    try:
+        movable = device_tensor(movable, torch.bool, "movable")
+    with _plan_for(topology_or_faces, p.shape[0]) as plan:
         return plan.run(p, steps, movable)
-    finally:
-        if owned:
-            torch.cuda.current_stream(p.device).synchronize()     # the plan's buffers are freed with it
-            plan.close()
 
 
 def scan_mask(initial_vs, original, eps: float = EPSILON) -> torch.Tensor:
     """bool [V], True = the vertex lies on the scan: its unsigned distance to the surface ``original`` is below ``eps``
     (``write_mask``, preprocess/prepare.py:98-100; ``EPSILON = 0.2`` there, on meshes of unit mean edge length).
     ``original``: a ``Surface``, a mesh object or a ``(vs, faces)`` pair."""
-    pts = _points(initial_vs)
+    pts = points(initial_vs)
     surf = original if isinstance(original, Surface) else Surface(original)
     if pts.device != surf.device:
         pts = pts.to(surf.device)
@@ -174,12 +170,12 @@ def prepare_inputs(initial, original, gt=None, rescale: bool = True, eps: float 
         raise ValueError(f"prepare_inputs: steps must be >= 0, got {steps}")
     ctx = torch.cuda.device(torch.device(device)) if device is not None and torch.cuda.is_available() else capi._NO_GUARD
     with ctx:
-        vs, faces = _vs_faces(initial)
+        vs, faces = vs_faces(initial)
         dev = vs.device if device is None else torch.device(device)
         if dev.type != "cuda":
             raise SemigcnLibraryError(f"prepare_inputs: device {dev} is not a HIP device (there is no CPU path)")
-        o_vs, o_faces = _vs_faces(original)
-        g_vs, g_faces = _vs_faces(gt) if gt is not None else (None, None)
+        o_vs, o_faces = vs_faces(original)
+        g_vs, g_faces = vs_faces(gt) if gt is not None else (None, None)
         vs, faces, o_vs, o_faces = vs.to(dev), faces.to(dev), o_vs.to(dev), o_faces.to(dev)
         if g_vs is not None:
             g_vs, g_faces = g_vs.to(dev), g_faces.to(dev)
@@ -192,26 +188,11 @@ def prepare_inputs(initial, original, gt=None, rescale: bool = True, eps: float 
                 g_vs = (g_vs.double() / scale).float()
         else:
             scale = torch.ones((), dtype=torch.float64, device=dev)
-        surf = Surface(o_vs, o_faces)
-        try:
+        with Surface(o_vs, o_faces) as surf:
             v_mask = scan_mask(vs, surf, eps)
-        finally:
-            torch.cuda.current_stream(dev).synchronize()
-            surf.close()
         x_pos = laplacian_smooth(vs, topo, steps)
         f_mask = meshprep.vmask_to_fmask(topo, v_mask)
         return Prepared(scale, vs, o_vs, o_faces, g_vs, g_faces, topo.faces, topo, v_mask, f_mask, x_pos, vs - x_pos, int(steps))
-
-
-def write_obj(path: str, vs, faces=None) -> None:
-    """The inverse of ``evaluate.read_obj``: ``v x y z`` lines with ``%.9g`` (a float32 round-trips bit for bit) and 1-based
-    ``f a b c`` lines; ``faces`` None or empty: vertices only."""
-    v = (vs.detach().cpu().numpy() if isinstance(vs, torch.Tensor) else np.asarray(vs)).reshape(-1, 3)
-    with open(path, "w") as f:
-        f.write("".join("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]) for p in v.tolist()))
-        if faces is not None:
-            fc = (faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)).reshape(-1, 3)
-            f.write("".join("f %d %d %d\n" % (t[0] + 1, t[1] + 1, t[2] + 1) for t in fc.tolist()))
 
 
 def main(argv=None) -> int:

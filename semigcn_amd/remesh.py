@@ -118,6 +118,7 @@ prints one JSON line with the sizes before and after, the rounds, the report and
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import math
 import sys
@@ -129,7 +130,8 @@ import torch
 
 from . import capi, prepare
 from .capi import RemeshPlan, SemigcnLibraryError
-from .evaluate import Surface, _vs_faces, read_obj
+from .evaluate import Surface
+from .mesh_common import Stages, check_mesh, read_obj, vs_faces, write_obj
 
 __all__ = ["split_long_edges", "collapse_short_edges", "flip_edges", "relax_project", "refine_mesh", "Split", "Collapsed",
            "Flipped", "Refined", "RemeshPlan", "split_threshold", "collapse_threshold", "CLOSING_PASSES"]
@@ -203,27 +205,6 @@ def _check_rounds(n, what):
     return n
 
 
-def _check_mesh(mesh):
-    """Shapes and dtypes of a tensor / array mesh, before any device is asked for."""
-    if isinstance(mesh, (tuple, list)) and len(mesh) == 2:
-        vs, faces = mesh
-    elif hasattr(mesh, "vs") and hasattr(mesh, "faces"):
-        vs, faces = mesh.vs, mesh.faces
-    else:
-        raise TypeError("expected a mesh with .vs / .faces or a (vs, faces) pair")
-    for x, name, kinds in ((vs, "vs", "f"), (faces, "faces", "iu")):
-        shape = tuple(x.shape) if hasattr(x, "shape") else np.asarray(x).shape
-        if len(shape) != 2 or shape[1] != 3:
-            raise ValueError(f"{name} must be [N, 3], got {shape}")
-        if isinstance(x, torch.Tensor):
-            ok = x.dtype.is_floating_point if kinds == "f" else x.dtype in (torch.int64, torch.int32)
-        else:
-            ok = np.asarray(x).dtype.kind in kinds
-        if not ok:
-            raise ValueError(f"{name} must hold {'floats' if kinds == 'f' else 'integers'}, got {getattr(x, 'dtype', type(x))}")
-    return mesh
-
-
 def _plan(vs: torch.Tensor, faces: torch.Tensor) -> RemeshPlan:
     plan = RemeshPlan(vs, faces)
     if not plan.valid:
@@ -239,49 +220,34 @@ def _plan(vs: torch.Tensor, faces: torch.Tensor) -> RemeshPlan:
 def split_long_edges(vs, faces, target: float, max_rounds: int = 64) -> Split:
     """Split every edge longer than 4/3 ``target`` (module docstring, 1.)."""
     target, max_rounds = _check_target(target), _check_rounds(max_rounds, "max_rounds")
-    _check_mesh((vs, faces))
-    vs, faces = _vs_faces(vs, faces)
+    vs, faces = vs_faces(*check_mesh((vs, faces)))
     with capi._on_device(vs.device):
-        plan = _plan(vs, faces)
-        try:
+        with _plan(vs, faces) as plan:
             counts, n_long = plan.split(split_threshold(target), max_rounds)
             out_vs, out_faces, parents, _ = plan.export()
-        finally:
-            torch.cuda.current_stream(vs.device).synchronize()     # the plan's buffers are freed with it
-            plan.close()
     return Split(out_vs, out_faces, parents, counts, n_long)
 
 
 def collapse_short_edges(vs, faces, target: float, max_rounds: int = 128) -> Collapsed:
     """Collapse the interior edges shorter than 4/5 ``target`` that the guards allow (module docstring, 2a.)."""
     target, max_rounds = _check_target(target), _check_rounds(max_rounds, "max_rounds")
-    _check_mesh((vs, faces))
-    vs, faces = _vs_faces(vs, faces)
+    vs, faces = vs_faces(*check_mesh((vs, faces)))
     with capi._on_device(vs.device):
-        plan = _plan(vs, faces)
-        try:
+        with _plan(vs, faces) as plan:
             counts, n_short = plan.collapse(collapse_threshold(target), split_threshold(target), max_rounds)
             out_vs, out_faces, _, _ = plan.export()
             vertex_ids, merged_into = plan.collapse_maps()
-        finally:
-            torch.cuda.current_stream(vs.device).synchronize()     # the plan's buffers are freed with it
-            plan.close()
     return Collapsed(out_vs, out_faces, vertex_ids, merged_into, counts, n_short)
 
 
 def flip_edges(vs, faces, max_rounds: int = 32) -> Flipped:
     """Flip edges towards valence 6 (4 on the border) (module docstring, 2.)."""
     max_rounds = _check_rounds(max_rounds, "max_rounds")
-    _check_mesh((vs, faces))
-    vs, faces = _vs_faces(vs, faces)
+    vs, faces = vs_faces(*check_mesh((vs, faces)))
     with capi._on_device(vs.device):
-        plan = _plan(vs, faces)
-        try:
+        with _plan(vs, faces) as plan:
             flips, before, after = plan.flip(max_rounds)
             _, out_faces, _, _ = plan.export()
-        finally:
-            torch.cuda.current_stream(vs.device).synchronize()
-            plan.close()
     return Flipped(out_faces, flips, before, after)
 
 
@@ -296,23 +262,12 @@ def relax_project(vs, faces, surface, steps: int = 1) -> torch.Tensor:
     """``steps`` Laplacian steps on the interior vertices, then their closest points on ``surface`` (a ``Surface``, a mesh
     object or a ``(vs, faces)`` pair) become the positions; border vertices never move (module docstring, 3.)."""
     steps = _check_rounds(steps, "steps")
-    _check_mesh((vs, faces))
-    vs, faces = _vs_faces(vs, faces)
+    vs, faces = vs_faces(*check_mesh((vs, faces)))
     with capi._on_device(vs.device):
-        plan = _plan(vs, faces)
-        try:
+        with _plan(vs, faces) as plan:
             border = plan.export()[3]
-        finally:
-            torch.cuda.current_stream(vs.device).synchronize()
-            plan.close()
-        owned = not isinstance(surface, Surface)
-        surf = Surface(surface) if owned else surface
-        try:
+        with (contextlib.nullcontext(surface) if isinstance(surface, Surface) else Surface(surface)) as surf:
             return _relax_project(vs, faces, border, surf, steps)
-        finally:
-            if owned:
-                torch.cuda.current_stream(vs.device).synchronize()
-                surf.close()
 
 
 def _edge_report(vs, faces, target: float) -> dict:
@@ -335,7 +290,6 @@ def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.
     split -> collapse -> flip -> relax_project (at most ``collapse_rounds`` rounds of 2a.); the vertices are renumbered, so
     ``Refined.parents`` is ``None``, and every iteration's report entry gains ``"collapse"`` and
     ``"n_short_after_collapse"``."""
-    from .holes import _Stages
     iterations = _check_rounds(iterations, "iterations")
     split_rounds, flip_rounds = _check_rounds(split_rounds, "split_rounds"), _check_rounds(flip_rounds, "flip_rounds")
     collapse_rounds = _check_rounds(collapse_rounds, "collapse_rounds")
@@ -344,8 +298,7 @@ def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.
         target = _check_target(target)
     else:
         target_percent = _check_target(target_percent, "target_percent")
-    _check_mesh(mesh)
-    vs, faces = _vs_faces(mesh)
+    vs, faces = vs_faces(*check_mesh(mesh))
     V0 = vs.shape[0]
     with capi._on_device(vs.device):
         if target is None:
@@ -355,23 +308,15 @@ def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.
             target = _check_target(target_percent / 100.0 * diag, "target (target_percent of the box diagonal)")
         thr2, lo2 = split_threshold(target), collapse_threshold(target)
         _plan(vs, faces).close()                                  # refuse an invalid input before anything is built
-        ms = {}
-
-        def add(stages):
-            for k, v in (stages.result() or {}).items():
-                ms[k] = ms.get(k, 0.0) + v
-
-        st = _Stages(vs.device, timings)
-        surf = Surface(vs, faces)
-        st.mark("surface")
-        add(st)
         parents = torch.arange(V0, dtype=torch.int64, device=vs.device)[:, None].repeat(1, 2)
         rounds, dev_start = [], None
-        try:
+        st = Stages(vs.device, timings)
+        with Surface(vs, faces) as surf:
+            st.mark("surface")
+            st.result()               # with timings: wait for the device here and after every iteration, as the figures always did
             for _ in range(iterations):
-                st = _Stages(vs.device, timings)
-                plan = _plan(vs, faces)
-                try:
+                st.mark(None)
+                with _plan(vs, faces) as plan:
                     if dev_start is None:
                         dev_start = plan.flip(0)[1]
                         st.mark("report")
@@ -383,14 +328,11 @@ def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.
                     flips, before, after = plan.flip(flip_rounds)
                     vs, faces, par, border = plan.export()
                     st.mark("flip")
-                finally:
-                    torch.cuda.current_stream(vs.device).synchronize()
-                    plan.close()
                 if not collapse:
                     parents = torch.cat([parents, par[parents.shape[0]:]])
                 vs = _relax_project(vs, faces, border, surf, relax_steps)
                 st.mark("relax")
-                add(st)
+                st.result()
                 rounds.append({"split": counts, "flip": flips, "n_long": n_long, "deviation_after_split": before,
                                "deviation_after_flip": after})
                 if collapse:
@@ -398,11 +340,10 @@ def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.
             # closing: relax_project can push an edge back over the threshold.  Split again (all rounds), project only what
             # was inserted, and repeat until a pass finds nothing to split: then no position changed after the last analysis,
             # so n_long == 0 in the report means that no edge of the RESULT has len2 > thr2, exactly.
-            st = _Stages(vs.device, timings)
+            st.mark(None)
             closing, n_long, dev_end = [], None, None
             for _ in range(CLOSING_PASSES + 1 if iterations > 0 else 1):
-                plan = _plan(vs, faces)
-                try:
+                with _plan(vs, faces) as plan:
                     last = len(closing) == CLOSING_PASSES or iterations == 0
                     counts, n_long = plan.split(thr2, 0 if last else split_rounds)
                     if not counts:
@@ -410,9 +351,6 @@ def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.
                         break
                     n_before = vs.shape[0]
                     vs, faces, par, border = plan.export()
-                finally:
-                    torch.cuda.current_stream(vs.device).synchronize()
-                    plan.close()
                 closing.append(sum(counts))
                 if not collapse:
                     parents = torch.cat([parents, par[n_before:]])
@@ -420,15 +358,11 @@ def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.
                 vs[n_before:] = torch.where(border[n_before:, None], vs[n_before:], closest)
             st.mark("split")
             dev_start = dev_end if dev_start is None else dev_start
-        finally:
-            torch.cuda.current_stream(vs.device).synchronize()
-            surf.close()
         report = {"target": target, "iterations": rounds, "closing": closing, "n_long": n_long, "deviation_start": dev_start, "deviation_end": dev_end,
                   "n_vertices": int(vs.shape[0]), "n_faces": int(faces.shape[0])}
         report.update(_edge_report(vs, faces, target))
         st.mark("report")
-        add(st)
-    return Refined(vs, faces, None if collapse else parents, report, ms if timings else None)
+        return Refined(vs, faces, None if collapse else parents, report, st.result())
 
 
 def main(argv=None) -> int:
@@ -461,8 +395,8 @@ def main(argv=None) -> int:
         out = refine_mesh(mesh, target=args.target, target_percent=args.target_percent, iterations=args.iterations, timings=True,
                           collapse=args.collapse)
     if args.output:
-        prepare.write_obj(args.output, out.vs, out.faces)
-    nv, nf = (int(x.shape[0]) for x in _vs_faces(mesh))
+        write_obj(args.output, out.vs, out.faces)
+    nv, nf = (int(x.shape[0]) for x in vs_faces(mesh))
     rep = dict(out.report)
     its = rep.pop("iterations")
     rep["n_closing"] = rep.pop("closing")
@@ -472,7 +406,7 @@ def main(argv=None) -> int:
     if args.collapse:
         rec.update({"n_collapsed": [sum(i["collapse"]) for i in its], "collapse_rounds": [len(i["collapse"]) for i in its]})
     rec.update(rep)
-    rec.update({k: round(v, 4) for k, v in out.stage_ms.items()})
+    rec.update(Stages.record(out.stage_ms))
     rec["total_ms"] = round(sum(out.stage_ms.values()), 4)
     print(json.dumps(rec))
     return 0

@@ -64,6 +64,7 @@ largest component, fill) with the detection that re-checks its result, and ``rem
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import sys
 from dataclasses import dataclass, field
@@ -74,8 +75,8 @@ import torch
 
 from . import capi, prepare
 from .capi import SemigcnLibraryError
-from .evaluate import Surface, _vs_faces, read_obj
-from .holes import _Stages         # the stage timer of the mesh modules (components uses it too)
+from .evaluate import Surface
+from .mesh_common import Stages, check_mesh, read_obj, vs_faces, write_obj
 
 __all__ = ["self_intersections", "remove_self_intersections", "repair", "fold_torus", "Intersections", "Repaired"]
 
@@ -103,29 +104,12 @@ class Repaired:
     vertex_ids: Optional[torch.Tensor] = None    # int64 [V'], new to original id, -1 for an inserted vertex
 
 
-def _check_shapes(mesh, faces=None):
-    """The ValueErrors that come before any device is asked for: faces must be [F, 3], vs [V, 3]."""
-    if faces is None:
-        if isinstance(mesh, (tuple, list)) and len(mesh) == 2:
-            mesh, faces = mesh
-        elif hasattr(mesh, "vs") and hasattr(mesh, "faces"):
-            mesh, faces = mesh.vs, mesh.faces
-        else:
-            raise TypeError("expected a mesh with .vs / .faces or a (vs, faces) pair")
-    for x, name in ((mesh, "vs"), (faces, "faces")):
-        shape = tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
-        if len(shape) != 2 or shape[1] != 3:
-            raise ValueError(f"{name} must be [{name[0].upper()}, 3], got {shape}")
-    return mesh, faces
-
-
 def self_intersections(vs, faces=None, surface: Optional[Surface] = None, timings: bool = False) -> Intersections:
     """The pairs of faces of ``(vs, faces)`` that cross (module docstring).  ``surface``: an ``evaluate.Surface`` already
     built from exactly these ``vs`` / ``faces`` -- the same device arrays, ``surface.vs`` and ``surface.faces``; anything
     else is a ``ValueError`` -- so that the hierarchy is not built twice; without it one is built and
     released.  One host synchronisation (the pair count).  ``timings``: also the device time of the stages."""
-    vs, faces = _check_shapes(vs, faces)
-    vs, faces = _vs_faces(vs, faces)
+    vs, faces = vs_faces(*check_mesh(vs, faces, dtypes=False))
     V, F = vs.shape[0], faces.shape[0]
     dev = vs.device
     if surface is not None:
@@ -139,10 +123,8 @@ def self_intersections(vs, faces=None, surface: Optional[Surface] = None, timing
         if F == 0:
             return Intersections(torch.zeros((0, 2), dtype=torch.int64, device=dev),
                                  torch.zeros(0, dtype=torch.bool, device=dev), 0, {} if timings else None)
-        st = _Stages(dev, timings)
-        own = surface is None
-        s = Surface(vs, faces) if own else surface
-        try:
+        st = Stages(dev, timings)
+        with (Surface(vs, faces) if surface is None else contextlib.nullcontext(surface)) as s:
             st.mark("tree")
             n_any, n_upper, n_deg = s._h.self_count(vs, faces)
             st.mark("count")
@@ -155,10 +137,6 @@ def self_intersections(vs, faces=None, surface: Optional[Surface] = None, timing
             st.mark("scan")
             pairs = s._h.self_pairs(vs, faces, offsets, P)
             st.mark("emit_sort")
-        finally:
-            if own:
-                torch.cuda.current_stream(dev).synchronize()     # the surface's buffers are freed with it
-                s.close()
         return Intersections(pairs, n_any > 0, int(n_degenerate), st.result())
 
 
@@ -209,7 +187,7 @@ def remove_self_intersections(mesh, grow: int = 1, max_rounds: int = 10, max_hol
     ``vs`` and ``faces`` bytes); ``max_rounds = 0`` only detects (``remaining = P``).  ``max_hole_edges`` and
     ``fair_steps`` go to ``holes.fill_holes``."""
     args = _check_loop_args(grow, max_rounds, max_hole_edges, fair_steps)
-    vs, faces = _vs_faces(*_check_shapes(mesh))
+    vs, faces = vs_faces(*check_mesh(mesh, dtypes=False))
     with capi._on_device(vs.device):
         return _loop(vs, faces, torch.arange(vs.shape[0], dtype=torch.int64, device=vs.device), *args)
 
@@ -221,7 +199,7 @@ def repair(mesh, grow: int = 1, max_rounds: int = 10, max_hole_edges: Optional[i
     the ``Repaired`` of the last step, its ``vertex_ids`` referring to the vertices of ``mesh``."""
     from . import components, holes
     args = _check_loop_args(grow, max_rounds, max_hole_edges, fair_steps)
-    vs, faces = _vs_faces(*_check_shapes(mesh))
+    vs, faces = vs_faces(*check_mesh(mesh, dtypes=False))
     with capi._on_device(vs.device):
         kept = components.keep_components((vs, faces), keep="largest")
         ids = kept.vertex_ids
@@ -290,7 +268,7 @@ def main(argv=None) -> int:
     if args.scan is not None:
         mesh = read_obj(args.scan)
         vs, faces, rep = repair(mesh, max_rounds=args.max_rounds, **kw)
-        prepare.write_obj(args.out_path, vs, faces)
+        write_obj(args.out_path, vs, faces)
         print(json.dumps({"n_vertices": int(mesh[0].shape[0]), "n_faces": int(mesh[1].shape[0]),
                           "out_vertices": int(vs.shape[0]), "out_faces": int(faces.shape[0]), "rounds": rep.rounds,
                           "removed_per_round": rep.removed_per_round, "remaining": rep.remaining}))
@@ -300,15 +278,15 @@ def main(argv=None) -> int:
         hits = self_intersections(vs, faces, timings=True)
     rec = {"n_vertices": int(vs.shape[0]), "n_faces": int(faces.shape[0]), "n_folds": args.fold, "n_pairs": len(hits),
            "n_flagged_faces": int(hits.face_mask.sum()), "n_degenerate": hits.n_degenerate}
-    rec.update({k: round(v, 4) for k, v in hits.stage_ms.items()})
-    st = _Stages(vs.device, True)
+    rec.update(Stages.record(hits.stage_ms))
+    st = Stages(vs.device, True)
     one = remove_self_intersections((vs, faces), max_rounds=1, **kw)
     st.mark("round")
-    rec["round_ms"] = round(st.result()["round_ms"], 4)
+    rec.update(Stages.record(st.result()))
     rec.update({"removed": one.removed_per_round, "out_vertices": int(one.vs.shape[0]), "out_faces": int(one.faces.shape[0]),
                 "remaining_after_round": one.remaining})
     if args.out:
-        prepare.write_obj(args.out, one.vs, one.faces)
+        write_obj(args.out, one.vs, one.faces)
     print(json.dumps(rec))
     return 0
 

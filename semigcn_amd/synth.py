@@ -240,13 +240,11 @@ def octahedron_sphere(level: int, seed: int = 314) -> SynthMesh:
     return SynthMesh(0, 0, vs, faces, edges, edge_index, z1, x_pos, v_mask)
 
 
-def write_obj(path: str, vs: np.ndarray, faces: np.ndarray) -> None:
-    """Minimal OBJ in the dialect util/mesh.py:35-58 parses (1-based ``f a b c``)."""
-    with open(path, "w") as f:
-        for p in vs:
-            f.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
-        for t in faces:
-            f.write("f %d %d %d\n" % (t[0] + 1, t[1] + 1, t[2] + 1))
+def write_obj(path: str, vs, faces=None) -> None:
+    """``mesh_common.write_obj`` (OBJ in the dialect util/mesh.py:35-58 parses); looked up when called, since that module
+    needs torch and this one does not."""
+    from .mesh_common import write_obj as write
+    write(path, vs, faces)
 
 
 def greedy_pool_hierarchy(edge_index: np.ndarray, num_vertices: int, ratio: float = 0.6,
