@@ -98,8 +98,9 @@ relax_project moves vertices, it can push an edge back over 4/3 target; after th
 closing passes therefore split again (all rounds) and project only the vertices they insert (border ones stay), until a
 pass finds no long edge: ``n_long == 0`` in the report then means that no edge of the RESULT has ``len2 > thr2``, exactly.
 The result is a valid ``initial`` for ``prepare.prepare_inputs``.  The report holds, per iteration, the split and flip counts per round,
-and for the result ``n_long`` (0 unless a cap ran out), ``n_short`` (edges below 4/5 target, which this stage does not
-treat), the min / mean / max edge length and the valence deviation at the start (the input) and the end.
+and for the result ``n_long`` (0 unless a cap ran out), ``n_short`` (the edges with ``len2 < lo2`` as 2a. defines it,
+counted by the closing plan; they are treated only with ``collapse=True``), the min / mean / max edge length and the valence
+deviation at the start (the input) and the end.
 
 Nothing here uses a float atomic; integer maxima and sums do not depend on order, so every output is bit-reproducible.
 Inputs are what ``evaluate`` accepts; HIP device only: a CPU tensor raises ``SemigcnLibraryError``.
@@ -270,15 +271,16 @@ def relax_project(vs, faces, surface, steps: int = 1) -> torch.Tensor:
             return _relax_project(vs, faces, border, surf, steps)
 
 
-def _edge_report(vs, faces, target: float) -> dict:
-    """Lengths of the unique edges (``meshprep.MeshTopology``): the counts against the target and min / mean / max."""
+def _edge_report(vs, faces, n_short: int) -> dict:
+    """Lengths of the unique edges (``meshprep.MeshTopology``): their number and min / mean / max.  ``n_short`` is handed in:
+    it is ``len2 < lo2`` as 2a. defines it, and the closing plan counts it."""
     from .meshprep import MeshTopology
     edges = MeshTopology(faces, vs.shape[0], vs.device, with_f2f=False).edges
     if edges.shape[0] == 0:
-        return {"n_edges": 0, "n_short": 0, "edge_min": None, "edge_mean": None, "edge_max": None}
+        return {"n_edges": 0, "n_short": n_short, "edge_min": None, "edge_mean": None, "edge_max": None}
     length = (vs[edges[:, 0]] - vs[edges[:, 1]]).norm(dim=1)
-    return {"n_edges": int(edges.shape[0]), "n_short": int((length < 0.8 * target).sum()),
-            "edge_min": float(length.min()), "edge_mean": float(prepare.mean_edge_length(vs, edges)), "edge_max": float(length.max())}
+    return {"n_edges": int(edges.shape[0]), "n_short": n_short, "edge_min": float(length.min()),
+            "edge_mean": float(prepare.mean_edge_length(vs, edges)), "edge_max": float(length.max())}
 
 
 def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.6, iterations: int = 5,
@@ -341,13 +343,14 @@ def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.
             # was inserted, and repeat until a pass finds nothing to split: then no position changed after the last analysis,
             # so n_long == 0 in the report means that no edge of the RESULT has len2 > thr2, exactly.
             st.mark(None)
-            closing, n_long, dev_end = [], None, None
+            closing, n_long, dev_end, n_short = [], None, None, None
             for _ in range(CLOSING_PASSES + 1 if iterations > 0 else 1):
                 with _plan(vs, faces) as plan:
                     last = len(closing) == CLOSING_PASSES or iterations == 0
                     counts, n_long = plan.split(thr2, 0 if last else split_rounds)
                     if not counts:
                         dev_end = plan.flip(0)[1]
+                        n_short = plan.collapse(lo2, thr2, 0)[1]          # no round: the count alone, len2 < lo2 as in 2a.
                         break
                     n_before = vs.shape[0]
                     vs, faces, par, border = plan.export()
@@ -360,7 +363,7 @@ def refine_mesh(mesh, target: Optional[float] = None, target_percent: float = 0.
             dev_start = dev_end if dev_start is None else dev_start
         report = {"target": target, "iterations": rounds, "closing": closing, "n_long": n_long, "deviation_start": dev_start, "deviation_end": dev_end,
                   "n_vertices": int(vs.shape[0]), "n_faces": int(faces.shape[0])}
-        report.update(_edge_report(vs, faces, target))
+        report.update(_edge_report(vs, faces, n_short))
         st.mark("report")
         return Refined(vs, faces, None if collapse else parents, report, st.result())
 
