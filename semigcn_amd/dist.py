@@ -300,6 +300,8 @@ class DistMeshGraph(_RowExchange):
     L^ on the owned AND ring-1 rows (Tx1 recomputed redundantly on ring 1 -- a few per cent of the rows), ``handle``
     on the owned rows only (Tx2).  Ring-2 rows carry no edges in ``handle_wide`` (their output rows are not used)."""
     sg_partitioned = True
+    #: one exchange serves both aggregations of a K = 3 ChebConv (functional.chebyshev_up / clenshaw_down take the shortcut)
+    two_ring = True
     #: True: a Sequential that meets this graph runs its runs of plain blocks phase by phase below the C ABI (part_blocks;
     #: set by partition_mgcn -- the SGCN's trainer calls part_chain itself)
     phases = False
@@ -1215,160 +1217,6 @@ def part_blocks(plans, graph: "DistMeshGraph", x_own: torch.Tensor, x_halo: Opti
     for p in plans:
         params.extend(p.param_tuple)
     return _PartChainFn.apply(pc, x_own, x_halo, *params)
-
-
-# --------------------------------------------------------------------------------------
-# ChebConv on a partition
-# --------------------------------------------------------------------------------------
-class _DistChebConvFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, g: DistMeshGraph, cache, moments, x, bias, *weights):
-        K, n = len(weights), g.n_own
-        C = x.shape[1]
-        from .functional import _wcat_pair, dense_nt
-        wcat, wcat_t = (_wcat_pair(weights, x.dtype) if cache is None
-                        else cache.get("cat", x.dtype, weights, None, lambda: _wcat_pair(weights, x.dtype)))
-        from .functional import _adopt_wide
-        T = _adopt_wide(x, K, g.n_ext) if K > 1 else None     # the fused BatchNorm in front may have written x in place
-        fresh = T is None
-        if fresh:
-            T = torch.empty((g.n_ext if K > 1 else n, K * C), dtype=x.dtype, device=x.device)
-        blk = [T[:, k * C:(k + 1) * C] for k in range(K)]
-        if fresh:
-            blk[0][:n].copy_(x)
-        if K == 3:       # ONE exchange (two rings of x): Tx1 on owned + ring-1 rows, Tx2 on the owned rows
-            g.exchange_and_aggregate_wide(blk[0], blk[0], blk[1], alpha=1.0)
-            g.aggregate(blk[1], blk[2][:n], alpha=2.0, X0=blk[0][:n], beta=-1.0)
-        else:
-            if K > 1:
-                g.exchange(blk[0])
-                g.aggregate(blk[0], blk[1][:n], alpha=1.0)
-            for k in range(2, K):
-                g.exchange(blk[k - 1])
-                g.aggregate(blk[k - 1], blk[k][:n], alpha=2.0, X0=blk[k - 2][:n], beta=-1.0)
-        out = dense_nt(T[:n], wcat, bias, moments=moments)    # (+ this rank's per-tile BatchNorm moments)
-        ctx.g, ctx.K, ctx.C = g, K, C
-        ctx.has_bias, ctx.param_dtype = bias is not None, weights[0].dtype
-        ctx.wcat_t = wcat_t
-        ctx.params = (bias, *weights)
-        ctx.save_for_backward(T, wcat)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        from .functional import _sink, column_sums, dense_nn, dense_nt, weight_grad
-        T, wcat = ctx.saved_tensors
-        g, K, C, n = ctx.g, ctx.K, ctx.C, ctx.g.n_own
-        dout = dout.contiguous()
-        need_x, need_b = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
-        dws = [None] * K
-        if any(ctx.needs_input_grad[5:]):
-            dwcat = weight_grad(dout, T[:n]).to(ctx.param_dtype)       # partial: summed over ranks later
-            dws = [dwcat[:, k * C:(k + 1) * C] for k in range(K)]
-        db = column_sums(dout).to(ctx.param_dtype) if (ctx.has_bias and need_b) else None
-        dx = None
-        if need_x:
-            dT = torch.empty((g.n_ext if K > 1 else n, K * C), dtype=dout.dtype, device=dout.device)
-            if ctx.wcat_t is not None:
-                dense_nt(dout, ctx.wcat_t, out=dT[:n])
-            else:
-                dense_nn(dout, wcat, out=dT[:n])
-            if K == 1:
-                dx = dT
-            else:
-                gk = [dT[:, k * C:(k + 1) * C] for k in range(K)]
-                dx = torch.empty((n, C), dtype=dout.dtype, device=dout.device)
-                if K == 3:   # ONE exchange of the [g1 | g2] column blocks on both rings; g1 += 2 L g2 on owned + ring 1
-                    g.exchange_and_aggregate_wide(dT[:, C:3 * C], gk[2], gk[1], alpha=2.0, X0=gk[1], beta=1.0)
-                    g.aggregate(gk[1], dx, alpha=1.0, X0=gk[0][:n], beta=1.0, X1=gk[2][:n], gamma=-1.0)
-                else:
-                    for k in range(K - 2, 0, -1):
-                        g.exchange(gk[k + 1])
-                        x1 = gk[k + 2][:n] if k + 2 <= K - 1 else None
-                        g.aggregate(gk[k + 1], gk[k][:n], alpha=2.0, X0=gk[k][:n], beta=1.0, X1=x1, gamma=-1.0)
-                    g.exchange(gk[1])
-                    x1 = gk[2][:n] if K >= 3 else None
-                    g.aggregate(gk[1], dx, alpha=1.0, X0=gk[0][:n], beta=1.0, X1=x1, gamma=-1.0)
-        if dout.is_cuda and _sink(ctx.params, (db, *dws)):      # this rank's partial sums, straight into the .grad accumulators
-            return (None, None, None, dx) + (None,) * (K + 1)
-        return (None, None, None, dx, db, *dws)
-
-
-class _DistChebConvPostFn(torch.autograd.Function):
-    """functional._ChebConvPostFn (GEMM first, Clenshaw aggregation after; for Cout < Cin) on a partition:
-    the halo rows exchanged are Cout wide instead of Cin wide."""
-
-    @staticmethod
-    def forward(ctx, g: DistMeshGraph, cache, x, bias, *weights):
-        K, n, Co = len(weights), g.n_own, weights[0].shape[0]
-        from .functional import _wstack_set, dense_nt
-
-        def build():      # the bias rides in on Z_0 (see functional._ChebConvPostFn)
-            return _wstack_set(weights, bias, x.dtype)
-        wstack, bias_k, wstack_t = build() if cache is None else cache.get("stack", x.dtype, weights, bias, build)
-        x = x if x.stride(1) == 1 else x.contiguous()
-        Z = torch.empty((g.n_ext, K * Co), dtype=x.dtype, device=x.device)
-        dense_nt(x, wstack, bias_k, out=Z[:n])
-        z = [Z[:, k * Co:(k + 1) * Co] for k in range(K)]
-        out = torch.empty((n, Co), dtype=x.dtype, device=x.device)
-        if K == 3:       # ONE exchange of [Z1 | Z2] on both rings; b1 = Z1 + 2 L Z2 on owned + ring 1
-            g.exchange_and_aggregate_wide(Z[:, Co:3 * Co], z[2], z[1], alpha=2.0, X0=z[1], beta=1.0)
-            g.aggregate(z[1], out, alpha=1.0, X0=z[0][:n], beta=1.0, X1=z[2][:n], gamma=-1.0)
-        else:
-            for k in range(K - 2, 0, -1):
-                g.exchange(z[k + 1])
-                x1 = z[k + 2][:n] if k + 2 <= K - 1 else None
-                g.aggregate(z[k + 1], z[k][:n], alpha=2.0, X0=z[k][:n], beta=1.0, X1=x1, gamma=-1.0)
-            g.exchange(z[1])
-            g.aggregate(z[1], out, alpha=1.0, X0=z[0][:n], beta=1.0, X1=z[2][:n] if K >= 3 else None, gamma=-1.0)
-        ctx.g, ctx.K, ctx.Co = g, K, Co
-        ctx.has_bias, ctx.param_dtype = bias is not None, weights[0].dtype
-        ctx.wstack_t = wstack_t
-        ctx.params = (bias, *weights)
-        ctx.save_for_backward(x, wstack)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        from .functional import _sink, column_sums, dense_nn, dense_nt, weight_grad
-        x, wstack = ctx.saved_tensors
-        g, K, Co, n = ctx.g, ctx.K, ctx.Co, ctx.g.n_own
-        dout = dout.contiguous()
-        G = torch.empty((g.n_ext, K * Co), dtype=dout.dtype, device=dout.device)
-        gk = [G[:, k * Co:(k + 1) * Co] for k in range(K)]
-        gk[0][:n].copy_(dout)
-        if K == 3:       # one exchange (two rings of dOut), as in _DistChebConvFn.forward
-            g.exchange_and_aggregate_wide(gk[0], gk[0], gk[1], alpha=1.0)
-            g.aggregate(gk[1], gk[2][:n], alpha=2.0, X0=gk[0][:n], beta=-1.0)
-        else:
-            g.exchange(gk[0])
-            g.aggregate(gk[0], gk[1][:n], alpha=1.0)
-            for k in range(2, K):
-                g.exchange(gk[k - 1])
-                g.aggregate(gk[k - 1], gk[k][:n], alpha=2.0, X0=gk[k - 2][:n], beta=-1.0)
-        own = G[:n]
-        dx = None
-        if ctx.needs_input_grad[2]:
-            dx = dense_nt(own, ctx.wstack_t) if ctx.wstack_t is not None else dense_nn(own, wstack)
-        dws = [None] * K
-        if any(ctx.needs_input_grad[4:]):
-            dwstack = weight_grad(own, x.contiguous()).to(ctx.param_dtype)
-            dws = [dwstack[k * Co:(k + 1) * Co] for k in range(K)]
-        db = column_sums(dout).to(ctx.param_dtype) if (ctx.has_bias and ctx.needs_input_grad[3]) else None
-        if dout.is_cuda and _sink(ctx.params, (db, *dws)):
-            return (None, None, dx) + (None,) * (K + 1)
-        return (None, None, dx, db, *dws)
-
-
-def dist_cheb_conv(g: DistMeshGraph, x, weights, bias=None, cache=None, moments=None):
-    """``moments``: as in functional.cheb_conv -- filled with this rank's per-row-tile moments when the layer's last step
-    is the MFMA product; the mesh-wide BatchNorm behind it merges them with the other ranks' (functional._BNActFn)."""
-    from . import functional as F_sg
-    if x.shape[0] != g.n_own:
-        raise ValueError(f"x has {x.shape[0]} rows but this rank owns {g.n_own} vertices")
-    if F_sg.AGGREGATE_AFTER_GEMM_WHEN_NARROWING and len(weights) >= 2 and weights[0].shape[0] < weights[0].shape[1]:
-        return _DistChebConvPostFn.apply(g, cache, x, bias, *weights)
-    return _DistChebConvFn.apply(g, cache, moments, x, bias, *weights)
 
 
 # --------------------------------------------------------------------------------------

@@ -441,28 +441,91 @@ def dense_nn(a: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = Non
         return run()
 
 
+# --------------------------------------------------------------------------------------------
+# ChebConv, module by module: on one device (graph.MeshGraph) and on one rank of a vertex partition (dist.DistMeshGraph).
+# Both graphs offer n_own / n_ext / exchange / aggregate / two_ring; a buffer has n_ext rows ([owned | halo]) and is
+# written on its owned rows.  On one device n_ext == n_own, exchange does nothing and every view below is the whole buffer.
+# --------------------------------------------------------------------------------------------
+def _blocks(g, buf: torch.Tensor, K: int):
+    """(the K column blocks of ``buf`` [n_ext, K*C], the same blocks on the owned rows)."""
+    C = buf.shape[1] // K
+    blk = [buf[:, k * C:(k + 1) * C] for k in range(K)]
+    return blk, (blk if g.n_ext == g.n_own else [b[:g.n_own] for b in blk])
+
+
+def chebyshev_up(g, buf: torch.Tensor, K: int, transpose: bool = False) -> None:
+    """T_1 = L^ T_0, T_k = 2 L^ T_(k-1) - T_(k-2) into blocks 1..K-1 of ``buf``; block 0 is final on the owned rows.
+    ``K == 3 and g.two_ring``: ONE exchange (two rings of T_0), T_1 on the owned and ring-1 rows, T_2 on the owned rows."""
+    blk, own = _blocks(g, buf, K)
+    if K == 3 and g.two_ring:
+        g.exchange_and_aggregate_wide(blk[0], blk[0], blk[1], alpha=1.0)
+        g.aggregate(blk[1], own[2], alpha=2.0, X0=own[0], beta=-1.0)
+        return
+    for k in range(1, K):
+        g.exchange(blk[k - 1])
+        if k == 1:
+            g.aggregate(blk[0], own[1], alpha=1.0, transpose=transpose)
+        else:
+            g.aggregate(blk[k - 1], own[k], alpha=2.0, X0=own[k - 2], beta=-1.0, transpose=transpose)
+
+
+def clenshaw_down(g, buf: torch.Tensor, K: int, out: torch.Tensor, transpose: bool = False) -> None:
+    """Clenshaw's recurrence b_k = z_k + 2 L^ b_(k+1) - b_(k+2), highest k first, in place in the blocks z_0..z_(K-1) of
+    ``buf`` (final on the owned rows; Y may alias X0), then ``out`` = z_0 + L^ b_1 - b_2 on the owned rows.  K >= 2.
+    ``K == 3 and g.two_ring``: ONE exchange of the [z_1 | z_2] column blocks on both rings, b_1 on the owned and ring-1 rows."""
+    blk, own = _blocks(g, buf, K)
+    if K == 3 and g.two_ring:
+        C = out.shape[1]
+        g.exchange_and_aggregate_wide(buf[:, C:3 * C], blk[2], blk[1], alpha=2.0, X0=blk[1], beta=1.0)
+        g.aggregate(blk[1], out, alpha=1.0, X0=own[0], beta=1.0, X1=own[2], gamma=-1.0)
+        return
+    for k in range(K - 2, 0, -1):
+        g.exchange(blk[k + 1])
+        x1 = own[k + 2] if k + 2 <= K - 1 else None
+        g.aggregate(blk[k + 1], own[k], alpha=2.0, X0=own[k], beta=1.0, X1=x1, gamma=-1.0, transpose=transpose)
+    g.exchange(blk[1])
+    g.aggregate(blk[1], out, alpha=1.0, X0=own[0], beta=1.0, X1=own[2] if K >= 3 else None, gamma=-1.0, transpose=transpose)
+
+
+def _owned(g, t: torch.Tensor) -> torch.Tensor:
+    """The owned rows of a buffer (the buffer itself where it has no others)."""
+    return t if t.shape[0] == g.n_own else t[:g.n_own]
+
+
+def _adopt(g, x: torch.Tensor, K: int):
+    """``_adopt_wide`` for a buffer over the graph's n_ext rows.  (Looked up by name at every call, and with two arguments
+    on one device: tests and tools put a two-argument function in its place.)"""
+    return _adopt_wide(x, K) if g.n_ext == g.n_own else _adopt_wide(x, K, g.n_ext)
+
+
+def _product_into(g, rows: int, cols: int, like: torch.Tensor, product) -> torch.Tensor:
+    """The [rows, cols] buffer whose owned rows ``product(out)`` fills.  On one device the product allocates its own
+    result (``out=None``: dense_nt's choice of engine looks at ``out``); on a partition it writes the owned rows of a
+    buffer that has the halo rows behind them."""
+    if g.n_ext == g.n_own:
+        return product(None)
+    buf = torch.empty((rows, cols), dtype=like.dtype, device=like.device)
+    product(buf[:g.n_own])
+    return buf
+
+
 class _ChebConvFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, graph: MeshGraph, cache: Optional[WeightCache], moments: Optional[dict], x: torch.Tensor,
+    def forward(ctx, graph, cache: Optional[WeightCache], moments: Optional[dict], x: torch.Tensor,
                 bias: Optional[torch.Tensor], *weights: torch.Tensor):
         K = len(weights)
-        V, C = x.shape
+        C = x.shape[1]
         wcat, wcat_t = (_wcat_pair(weights, x.dtype) if cache is None
                         else cache.get("cat", x.dtype, weights, None, lambda: _wcat_pair(weights, x.dtype)))
         if K == 1:
             T = x.contiguous()
         else:
-            T = _adopt_wide(x, K)
-            fresh = T is None
-            if fresh:
-                T = torch.empty((V, K * C), dtype=x.dtype, device=x.device)
-            blk = [T[:, k * C:(k + 1) * C] for k in range(K)]
-            if fresh:
-                blk[0].copy_(x)
-            graph.aggregate(blk[0], blk[1], alpha=1.0)
-            for k in range(2, K):
-                graph.aggregate(blk[k - 1], blk[k], alpha=2.0, X0=blk[k - 2], beta=-1.0)
-        out = dense_nt(T, wcat, bias, moments=moments)
+            T = _adopt(graph, x, K)        # the fused BatchNorm in front may have written x into block 0 already
+            if T is None:
+                T = torch.empty((graph.n_ext, K * C), dtype=x.dtype, device=x.device)
+                T[:graph.n_own, :C].copy_(x)
+            chebyshev_up(graph, T, K)
+        out = dense_nt(_owned(graph, T), wcat, bias, moments=moments)   # (on a partition: this rank's rows and tile moments)
         ctx.graph, ctx.K, ctx.C = graph, K, C
         ctx.has_bias = bias is not None
         ctx.param_dtype = weights[0].dtype
@@ -475,31 +538,27 @@ class _ChebConvFn(torch.autograd.Function):
     def backward(ctx, dout: torch.Tensor):
         T, wcat = ctx.saved_tensors
         graph, K, C = ctx.graph, ctx.K, ctx.C
+        n = graph.n_own
         need_x, need_b = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
         db = column_sums(dout).to(ctx.param_dtype) if (ctx.has_bias and need_b) else None   # (may be known from the producer)
         dout = dout.contiguous()
         need_w = any(ctx.needs_input_grad[5:])
         dws = [None] * K
         if need_w:
-            dwcat = weight_grad(dout, T).to(ctx.param_dtype)  # [Cout, K*C], reduced over V in fp32
+            # [Cout, K*C], reduced over the owned rows in fp32 (on a partition: a partial sum, added over the ranks later)
+            dwcat = weight_grad(dout, _owned(graph, T)).to(ctx.param_dtype)
             dws = [dwcat[:, k * C:(k + 1) * C] for k in range(K)]
         dx = None
         if need_x:
-            # [V, K*C]; block k = dL/dTx_k before the recurrence is unwound
-            dT = dense_nt(dout, ctx.wcat_t) if ctx.wcat_t is not None else dense_nn(dout, wcat)
+            # block k = dL/dTx_k before the recurrence is unwound: g_k += 2 L^T g_(k+1) - g_(k+2), highest k first
+            dT = _product_into(graph, graph.n_ext if K > 1 else n, K * C, dout,
+                               lambda out: dense_nt(dout, ctx.wcat_t, out=out) if ctx.wcat_t is not None
+                               else dense_nn(dout, wcat, out=out))
             if K == 1:
                 dx = dT
             else:
-                g = [dT[:, k * C:(k + 1) * C] for k in range(K)]
-                tr = not graph.symmetric
-                # g_k += 2 L^T g_(k+1) - g_(k+2), highest k first, in place (Y may alias X0)
-                for k in range(K - 2, 0, -1):
-                    x1 = g[k + 2] if k + 2 <= K - 1 else None
-                    graph.aggregate(g[k + 1], g[k], alpha=2.0, X0=g[k], beta=1.0, X1=x1, gamma=-1.0,
-                                    transpose=tr)
-                dx = torch.empty((T.shape[0], C), dtype=dout.dtype, device=dout.device)
-                x1 = g[2] if K >= 3 else None
-                graph.aggregate(g[1], dx, alpha=1.0, X0=g[0], beta=1.0, X1=x1, gamma=-1.0, transpose=tr)
+                dx = torch.empty((n, C), dtype=dout.dtype, device=dout.device)
+                clenshaw_down(graph, dT, K, dx, transpose=not graph.symmetric)
         if dout.is_cuda and _sink(ctx.params, (db, *dws)):
             return (None, None, None, dx) + (None,) * (K + 1)
         return (None, None, None, dx, db, *dws)
@@ -520,13 +579,13 @@ def _wstack_set(weights, bias, dtype):
 class _ChebConvPostFn(torch.autograd.Function):
     """The same operator with the aggregation AFTER the GEMM, for layers that narrow (Cout < Cin):
     L^ is linear, so  sum_k T_k(L^) x W_k^T = sum_k T_k(L^) Z_k  with  Z = x [W_0|..|W_(K-1)]^T,
-    evaluated by Clenshaw's recurrence  b_k = Z_k + 2 L^ b_(k+1) - b_(k+2),  out = Z_0 + L^ b_1 - b_2.
-    The GEMM has the same FLOPs, but every aggregation is Cout wide instead of Cin wide, and only x
-    is kept for backward (not the [V, K*Cin] buffer).  Backward: G = [T_0|T_1|..](L^T) dOut is the
+    evaluated by Clenshaw's recurrence (``clenshaw_down``).
+    The GEMM has the same FLOPs, but every aggregation (and every halo row exchanged) is Cout wide instead of Cin wide,
+    and only x is kept for backward (not the [V, K*Cin] buffer).  Backward: G = [T_0|T_1|..](L^T) dOut is the
     forward Chebyshev recurrence applied to dOut, then dx = G Wstack, dWstack = G^T x."""
 
     @staticmethod
-    def forward(ctx, graph: MeshGraph, cache: Optional[WeightCache], x, bias, *weights):
+    def forward(ctx, graph, cache: Optional[WeightCache], x, bias, *weights):
         K = len(weights)
         Co = weights[0].shape[0]
 
@@ -534,15 +593,10 @@ class _ChebConvPostFn(torch.autograd.Function):
             return _wstack_set(weights, bias, x.dtype)
         wstack, bias_k, wstack_t = build() if cache is None else cache.get("stack", x.dtype, weights, bias, build)
         x = x if x.stride(1) == 1 else x.contiguous()
-        # the bias rides in on Z_0 (coefficient +1 in the recurrence): free in the GEMM epilogue
-        Z = dense_nt(x, wstack, bias_k)                              # [V, K*Cout]
-        z = [Z[:, k * Co:(k + 1) * Co] for k in range(K)]
-        # Clenshaw, in place in Z: after step k, z[k] holds b_k
-        for k in range(K - 2, 0, -1):
-            x1 = z[k + 2] if k + 2 <= K - 1 else None
-            graph.aggregate(z[k + 1], z[k], alpha=2.0, X0=z[k], beta=1.0, X1=x1, gamma=-1.0)
-        out = torch.empty((x.shape[0], Co), dtype=x.dtype, device=x.device)
-        graph.aggregate(z[1], out, alpha=1.0, X0=z[0], beta=1.0, X1=z[2] if K >= 3 else None, gamma=-1.0)
+        # [n_ext, K*Cout]; the bias rides in on Z_0 (coefficient +1 in the recurrence): free in the GEMM epilogue
+        Z = _product_into(graph, graph.n_ext, K * Co, x, lambda out: dense_nt(x, wstack, bias_k, out=out))
+        out = torch.empty((graph.n_own, Co), dtype=x.dtype, device=x.device)
+        clenshaw_down(graph, Z, K, out)
         ctx.graph, ctx.K, ctx.Co = graph, K, Co
         ctx.has_bias, ctx.param_dtype = bias is not None, weights[0].dtype
         ctx.wstack_t = wstack_t
@@ -554,25 +608,22 @@ class _ChebConvPostFn(torch.autograd.Function):
     def backward(ctx, dout):
         x, wstack = ctx.saved_tensors
         graph, K, Co = ctx.graph, ctx.K, ctx.Co
-        V = dout.shape[0]
-        tr = not graph.symmetric
         db = column_sums(dout).to(ctx.param_dtype) if (ctx.has_bias and ctx.needs_input_grad[3]) else None
-        G = _adopt_wide(dout, K)          # the fused BatchNorm backward writes dout into block 0 of a [V, K*Co] buffer
+        # the fused BatchNorm backward writes dout into block 0 of a [V, K*Co] buffer.  (Only on one device: behind a
+        # partitioned conv it is asked for a plain gradient -- nn.Sequential, grad_widen -- so nothing is adopted there.)
+        G = _adopt(graph, dout, K)
         if G is None:
             dout = dout.contiguous()
-            G = torch.empty((V, K * Co), dtype=dout.dtype, device=dout.device)
-            G[:, :Co].copy_(dout)
-        g = [G[:, k * Co:(k + 1) * Co] for k in range(K)]
-        dout = g[0]
-        graph.aggregate(g[0], g[1], alpha=1.0, transpose=tr)
-        for k in range(2, K):
-            graph.aggregate(g[k - 1], g[k], alpha=2.0, X0=g[k - 2], beta=-1.0, transpose=tr)
+            G = torch.empty((graph.n_ext, K * Co), dtype=dout.dtype, device=dout.device)
+            G[:graph.n_own, :Co].copy_(dout)
+        chebyshev_up(graph, G, K, transpose=not graph.symmetric)
+        own = _owned(graph, G)
         dx = None
         if ctx.needs_input_grad[2]:
-            dx = dense_nt(G, ctx.wstack_t) if ctx.wstack_t is not None else dense_nn(G, wstack)
+            dx = dense_nt(own, ctx.wstack_t) if ctx.wstack_t is not None else dense_nn(own, wstack)
         dws = [None] * K
         if any(ctx.needs_input_grad[4:]):
-            dwstack = weight_grad(G, x.contiguous()).to(ctx.param_dtype)   # [K*Cout, Cin]
+            dwstack = weight_grad(own, x.contiguous()).to(ctx.param_dtype)   # [K*Cout, Cin]
             dws = [dwstack[k * Co:(k + 1) * Co] for k in range(K)]
         if dout.is_cuda and _sink(ctx.params, (db, *dws)):
             return (None, None, dx) + (None,) * (K + 1)
@@ -584,23 +635,29 @@ class _ChebConvPostFn(torch.autograd.Function):
 AGGREGATE_AFTER_GEMM_WHEN_NARROWING = True
 
 
-def cheb_conv(graph: MeshGraph, x: torch.Tensor, weights: Sequence[torch.Tensor],
+def aggregates_after_product(K: int, Cin: int, Cout: int) -> bool:
+    """The evaluation order of a ChebConv layer: True = product first, Clenshaw aggregation after (_ChebConvPostFn)."""
+    return AGGREGATE_AFTER_GEMM_WHEN_NARROWING and K >= 2 and Cout < Cin
+
+
+def cheb_conv(graph, x: torch.Tensor, weights: Sequence[torch.Tensor],
               bias: Optional[torch.Tensor] = None, cache: Optional[WeightCache] = None,
               moments: Optional[dict] = None) -> torch.Tensor:
-    """ChebConv forward on a prepared graph; ``weights[k]`` is ``lins[k].weight`` [Cout, Cin].  ``cache``: the
-    calling layer's WeightCache (optional).  ``moments``: a dict that receives the output's per-row-tile column
-    moments when the layer's last step is the MFMA product (see dense_nt) -- the BatchNorm behind it then skips its
-    own moments pass; it stays empty otherwise."""
+    """ChebConv forward on a prepared graph (a MeshGraph, or one rank's DistMeshGraph: ``x`` holds the rows this rank
+    owns); ``weights[k]`` is ``lins[k].weight`` [Cout, Cin].  ``cache``: the calling layer's WeightCache (optional).
+    ``moments``: a dict that receives the output's per-row-tile column moments when the layer's last step is the MFMA
+    product (see dense_nt) -- the BatchNorm behind it then skips its own moments pass (a mesh-wide one merges them with
+    the other ranks', _BNActFn); it stays empty otherwise."""
     if x.dim() != 2:
         raise ValueError(f"x must be [V, C], got {tuple(x.shape)}")
-    if getattr(graph, "sg_partitioned", False):
-        from .dist import dist_cheb_conv
-        return dist_cheb_conv(graph, x, weights, bias, cache, moments)
-    if x.shape[0] != graph.num_vertices:
-        raise ValueError(f"x has {x.shape[0]} rows but the graph has {graph.num_vertices} vertices")
-    if AGGREGATE_AFTER_GEMM_WHEN_NARROWING and len(weights) >= 2 and weights[0].shape[0] < weights[0].shape[1]:
+    if x.shape[0] != graph.n_own:
+        what = "this rank owns" if graph.n_ext != graph.n_own else "the graph has"
+        raise ValueError(f"x has {x.shape[0]} rows but {what} {graph.n_own} vertices")
+    if aggregates_after_product(len(weights), weights[0].shape[1], weights[0].shape[0]):
         return _ChebConvPostFn.apply(graph, cache, x, bias, *weights)
     return _ChebConvFn.apply(graph, cache, moments, x, bias, *weights)
+
+
 
 
 class _LaplacianFn(torch.autograd.Function):
@@ -1102,7 +1159,7 @@ class BlockPlan:
     def __init__(self, conv, bn, slope: float, pool=None):
         self.conv, self.bn, self.pool, self.slope = conv, bn, pool, float(slope)
         self.K, self.Cin, self.Cout = conv.K, conv.in_channels, conv.out_channels
-        self.order = 1 if (AGGREGATE_AFTER_GEMM_WHEN_NARROWING and self.K >= 2 and self.Cout < self.Cin) else 0
+        self.order = 1 if aggregates_after_product(self.K, self.Cin, self.Cout) else 0
         self.pool_mode = 0 if pool is None else int(pool.sg_pool_mode)
         self._packs: dict = {}         # dtype -> [version sum at the last packing, wpack, wpack_t, wpack32, wpack32_t, bias_k]
         self._static: dict = {}        # (dtype, device) -> bool, for the parameter tensors of `_mark`

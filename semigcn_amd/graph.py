@@ -21,9 +21,15 @@ class MeshGraph:
     """Scaled Laplacian ``L^ = -D^-1/2 A D^-1/2`` of one mesh ``edge_index``
     ([2, E] int64, reference layout util/mesh.py:229-230) as a device CSR."""
 
+    #: The surface the ChebConv recurrences are written against (functional.chebyshev_up / clenshaw_down), shared with a
+    #: rank's share of a vertex partition (dist.DistMeshGraph): feature buffers have ``n_ext`` rows of which the first
+    #: ``n_own`` are this graph's own, ``exchange`` fills the others, and ``two_ring`` says that ONE exchange serves both
+    #: aggregations of a K = 3 layer.  On one device every row is owned and there is nothing to exchange.
+    two_ring = False
+
     def __init__(self, handle: capi.GraphHandle, num_vertices: int, num_edges: int):
         self.handle = handle
-        self.num_vertices = num_vertices
+        self.num_vertices = self.n_own = self.n_ext = num_vertices
         self.num_edges = num_edges  # directed, as given (self-loops included)
         if type(self).aggregate is MeshGraph.aggregate:
             self.aggregate = handle.spmm       # the bound method itself: one Python frame less per launch
@@ -43,6 +49,9 @@ class MeshGraph:
 
     def aggregate(self, X, Y, **kw):
         return self.handle.spmm(X, Y, **kw)
+
+    def exchange(self, block) -> None:
+        """No halo rows: nothing to fetch."""
 
     def new_like(self, X: torch.Tensor, cols: Optional[int] = None) -> torch.Tensor:
         return torch.empty((self.handle.num_rows, X.shape[1] if cols is None else cols),

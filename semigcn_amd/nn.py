@@ -99,14 +99,13 @@ class ChebConv(nn.Module):
     def input_buffer_blocks(self) -> int:
         """K when this layer evaluates [Tx0|..|Tx(K-1)] next to its input (so a producer may write the
         input straight into the first block of a [V, K*Cin] buffer), 1 when it aggregates after the GEMM."""
-        post = F_sg.AGGREGATE_AFTER_GEMM_WHEN_NARROWING and self.K >= 2 and self.out_channels < self.in_channels
+        post = F_sg.aggregates_after_product(self.K, self.in_channels, self.out_channels)
         return 1 if (post or self.K == 1) else self.K
 
     def grad_buffer_blocks(self) -> int:
         """K when the backward pass runs the Chebyshev recurrence on the OUTPUT gradient (aggregate-after-GEMM
         layers): the producer of that gradient may then write it straight into block 0 of a [V, K*Cout] buffer."""
-        post = F_sg.AGGREGATE_AFTER_GEMM_WHEN_NARROWING and self.K >= 2 and self.out_channels < self.in_channels
-        return self.K if post else 1
+        return self.K if F_sg.aggregates_after_product(self.K, self.in_channels, self.out_channels) else 1
 
     def forward(self, x: Tensor, edge_index: Union[Tensor, MeshGraph], edge_weight=None, batch=None,
                 lambda_max=None, moments: Optional[dict] = None) -> Tensor:

@@ -24,6 +24,30 @@ def _install_doubles():
     capi.gather_rows = lambda rows, X, out=None: X.index_select(0, rows.long())
 
 
+GENERAL_KS = (1, 2, 4)            # K = 3 takes the two-ring shortcut; every other K the loop with one exchange per aggregation
+
+
+def _general_loop_layers(g, x_all, r_all):
+    """ChebConv(12, 20, K) (aggregate first) and ChebConv(20, 12, K) (product first for K >= 2) on this rank's rows:
+    outputs, input gradients, reduced parameter gradients and the number of halo exchanges they took."""
+    import golden_util as GU
+    from semigcn_amd import dist as sgdist, nn as sgnn
+    out, before = {}, sgdist.collective_counts["all_to_all"]
+    for K in GENERAL_KS:
+        for xs, rs in ((x_all, r_all), (r_all, x_all)):
+            conv = sgnn.ChebConv(xs.shape[1], rs.shape[1], K=K)
+            GU.fill_state(conv, seed=10 * K + xs.shape[1])
+            x = xs[g.start:g.end].clone().requires_grad_(True)
+            y = conv(x, g)
+            (y * rs[g.start:g.end]).sum().backward()
+            sgdist.all_reduce_gradients(list(conv.parameters()))
+            key = f"gen_K{K}_{xs.shape[1]}_{rs.shape[1]}"
+            out[key + "_y"], out[key + "_dx"] = y.detach().clone(), x.grad.clone()
+            out[key + "_dw"], out[key + "_db"] = conv.lins[K - 1].weight.grad.clone(), conv.bias.grad.clone()
+    out["gen_all_to_all"] = sgdist.collective_counts["all_to_all"] - before
+    return out
+
+
 def _run_rank(rank, world, port, out_dir, skip):
     _install_doubles()
     torch.set_num_threads(1)
@@ -77,6 +101,7 @@ def _run_rank(rank, world, port, out_dir, skip):
            "conv2_dw": conv2.lins[1].weight.grad.clone(), "conv2_db": conv2.bias.grad.clone(), "bn_y": yb.detach().clone(), "bn_dx": xb.grad.clone(),
            "bn_dw": bn.weight.grad.clone(), "bn_db": bn.bias.grad.clone(),
            "bn_rm": bn.running_mean.clone(), "bn_rv": bn.running_var.clone()}
+    lin.update(_general_loop_layers(g, x_all, r_all))
 
     tr = sgdist.DistSGCNTrainer(model, part, accumulate=2)
     # (1) one forward/backward on the initial parameters, gradients reduced explicitly
@@ -140,6 +165,17 @@ def test_partitioned_training_matches_single_rank(world, skip):
     for key in ("conv_dw", "conv_db", "conv2_dw", "conv2_db", "bn_dw", "bn_db", "bn_rm", "bn_rv"):
         for p in parts:
             assert rel_l2(p["lin"][key], ref["lin"][key]) < 5e-6, key
+    # the general loop of the two recurrences (K != 3), both evaluation orders: the same bounds, and exactly one halo
+    # exchange per aggregation -- (K - 1) per layer and pass, two layers per K, forward and backward
+    for key in (f"gen_K{K}_{io}" for K in GENERAL_KS for io in ("12_20", "20_12")):
+        for t in ("_y", "_dx"):
+            assert rel_l2(torch.cat([p["lin"][key + t] for p in parts], dim=0), ref["lin"][key + t]) < 2e-6, key + t
+        for t in ("_dw", "_db"):
+            for p in parts:
+                assert rel_l2(p["lin"][key + t], ref["lin"][key + t]) < 5e-6, key + t
+    assert ref["lin"]["gen_all_to_all"] == 0
+    for p in parts:
+        assert p["lin"]["gen_all_to_all"] == 2 * sum(K - 1 for K in GENERAL_KS) * 2 == 16
     for p in parts:
         assert torch.equal(p["lin"]["mm_lo"], ref["lin"]["mm_lo"]) and torch.equal(p["lin"]["mm_hi"], ref["lin"]["mm_hi"])
     mm_dz = torch.cat([p["lin"]["mm_dz"] for p in parts], dim=0)
