@@ -553,6 +553,27 @@ SG_API int sg_parts_emit(sg_parts* p, const float* vs, float* new_vs, int64_t* n
  *   vertex of the input, the two ends (lo, hi) of the split edge otherwise) and,
  *   when not null, border uint8 [V] (1 = the vertex is on a border edge).
  *   Asynchronous.
+ * sg_remesh_set_feature: enabled != 0 turns the crease rules on for every later
+ *   call on this plan, with cos_t the cosine of the feature angle (-1 < cos_t
+ *   < 1): an edge with two faces whose normals turn by more than the angle is a
+ *   crease; flips skip it, collapses keep corners and move crease-line vertices
+ *   only along their crease (semigcn_amd/remesh.py, "Creases").  enabled == 0
+ *   (the state sg_remesh_create leaves) adds no launch.  Touches no device.
+ * sg_remesh_features: analyses the mesh as it stands and writes vclass uint8
+ *   [V] (device; 0 smooth, 1 crease-line, 2 corner, 3 border) and crease_nbr
+ *   int64 [V,2] (device; the two crease neighbours (lo, hi) of a crease-line
+ *   vertex, (-1, -1) otherwise); *n_crease (host) is the number C of crease
+ *   edges.  With the setting off C = 0 and the classes are 0 or 3.  One stream
+ *   synchronisation when the setting is on.  V = 0 touches no device.
+ * sg_remesh_crease_edges: writes the C crease edges of the last
+ *   sg_remesh_features, edges int64 [C,2] (device) in ascending (lo, hi); any
+ *   other operation on the plan in between invalidates them (SG_ERR_INVALID).
+ *   Asynchronous.
+ * sg_crease_step: one Jacobi step along the creases, no plan needed: out[v] =
+ *   (in[v] + in[lo] + in[hi]) / 3 in float32, summed in that order, where
+ *   crease_nbr[v] = (lo, hi) with both in [0, V); every other row is copied.
+ *   in, out float32 [V,3], crease_nbr int64 [V,2] (device); in != out.
+ *   Asynchronous.
  * ------------------------------------------------------------------------- */
 typedef struct sg_remesh sg_remesh;
 SG_API int sg_remesh_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, void* stream, sg_remesh** out);
@@ -565,6 +586,10 @@ SG_API int sg_remesh_collapse(sg_remesh* p, float lo2, float thr2, int64_t max_r
                               int64_t* n_rounds, int64_t* n_short);
 SG_API int sg_remesh_collapse_maps(const sg_remesh* p, int64_t* vertex_ids, int64_t* merged_into, void* stream);
 SG_API int sg_remesh_export(const sg_remesh* p, float* vs, int64_t* faces, int64_t* parents, uint8_t* border, void* stream);
+SG_API int sg_remesh_set_feature(sg_remesh* p, int enabled, double cos_t);
+SG_API int sg_remesh_features(sg_remesh* p, void* stream, uint8_t* vclass, int64_t* crease_nbr, int64_t* n_crease);
+SG_API int sg_remesh_crease_edges(const sg_remesh* p, int64_t* edges, void* stream);
+SG_API int sg_crease_step(const float* in, float* out, const int64_t* crease_nbr, int64_t V, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Loss step of the training loop, fused -- replaces Models.compute_fn

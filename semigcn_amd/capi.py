@@ -227,6 +227,10 @@ _SIGNATURES = {
                                    POINTER(c_int64)]),
     "sg_remesh_collapse_maps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_remesh_export": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_remesh_set_feature": (c_int, [c_void_p, c_int, ctypes.c_double]),
+    "sg_remesh_features": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
+    "sg_remesh_crease_edges": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "sg_crease_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None
@@ -1740,6 +1744,47 @@ class RemeshPlan(_OwnedHandle):
             _check(load().sg_remesh_export(self._h, none_if_empty(vs), none_if_empty(faces), none_if_empty(parents),
                                            none_if_empty(border), _stream(vs)), "sg_remesh_export")
         return vs, faces, parents, border
+
+    def set_feature(self, cos_t: Optional[float]):
+        """Turn the crease rules on with the cosine ``cos_t`` of the feature angle (``remesh.feature_cos``), or off with
+        ``None`` (the state of a new plan).  Holds for every later call on the plan."""
+        self._open()
+        _check(load().sg_remesh_set_feature(self._h, 0 if cos_t is None else 1, 0.0 if cos_t is None else float(cos_t)),
+               "sg_remesh_set_feature")
+
+    def features(self):
+        """(vclass uint8 [V]: 0 smooth, 1 crease-line, 2 corner, 3 border; crease_nbr int64 [V, 2]: (lo, hi) of a
+        crease-line vertex, (-1, -1) otherwise; crease edges int64 [C, 2] in ascending (lo, hi)) of the mesh as it stands."""
+        self._open()
+        V = self.num_vertices
+        vclass = torch.empty(V, dtype=torch.uint8, device=self.device)
+        nbr = torch.empty((V, 2), dtype=torch.int64, device=self.device)
+        none_if_empty = lambda t: _ptr(t) if t.numel() else None
+        n_crease = c_int64()
+        with _on_device(self.device):
+            _check(load().sg_remesh_features(self._h, _raw_stream_of(self.device), none_if_empty(vclass), none_if_empty(nbr),
+                                             byref(n_crease)), "sg_remesh_features")
+            edges = torch.empty((int(n_crease.value), 2), dtype=torch.int64, device=self.device)
+            _check(load().sg_remesh_crease_edges(self._h, none_if_empty(edges), _raw_stream_of(self.device)),
+                   "sg_remesh_crease_edges")
+        return vclass, nbr, edges
+
+
+def crease_step(vs: torch.Tensor, crease_nbr: torch.Tensor) -> torch.Tensor:
+    """One Jacobi step along the creases (sg_crease_step): row ``v`` with ``crease_nbr[v] = (lo, hi) >= 0`` becomes
+    ``(vs[v] + vs[lo] + vs[hi]) / 3`` in float32, every other row is copied."""
+    _require_device(vs, "vs")
+    _require_device(crease_nbr, "crease_nbr")
+    vs = _vs_arg(vs).detach().contiguous()
+    if crease_nbr.dtype != torch.int64 or tuple(crease_nbr.shape) != (vs.shape[0], 2) or crease_nbr.device != vs.device:
+        raise SemigcnLibraryError(f"crease_nbr must be int64 [{vs.shape[0]}, 2] on {vs.device}, got {crease_nbr.dtype} "
+                                  f"{tuple(crease_nbr.shape)} on {crease_nbr.device}")
+    crease_nbr = crease_nbr.contiguous()
+    out = torch.empty_like(vs)
+    if vs.shape[0]:
+        with _on_device(vs.device):
+            _check(load().sg_crease_step(_ptr(vs), _ptr(out), _ptr(crease_nbr), vs.shape[0], _stream(vs)), "sg_crease_step")
+    return out
 
 
 def _raw_stream_of(device: torch.device) -> int:

@@ -700,6 +700,31 @@ SG_API int sg_remesh_export(const sg_remesh* p, float* vs, int64_t* faces, int64
   return remesh_export(p, vs, faces, parents, border, (hipStream_t)stream);
 }
 
+SG_API int sg_remesh_set_feature(sg_remesh* p, int enabled, double cos_t) {
+  SG_REQUIRE(p != nullptr, "sg_remesh_set_feature: null plan");
+  SG_REQUIRE(!enabled || (cos_t > -1.0 && cos_t < 1.0), "sg_remesh_set_feature: cos_t must lie in (-1, 1)");   // false for a NaN
+  remesh_set_feature(p, enabled != 0, cos_t);
+  return SG_OK;
+}
+
+SG_API int sg_remesh_features(sg_remesh* p, void* stream, uint8_t* vclass, int64_t* crease_nbr, int64_t* n_crease) {
+  SG_REQUIRE(p != nullptr, "sg_remesh_features: null plan");
+  SG_REQUIRE(n_crease != nullptr, "sg_remesh_features: null pointer");
+  return remesh_features(p, (hipStream_t)stream, vclass, crease_nbr, n_crease);
+}
+
+SG_API int sg_remesh_crease_edges(const sg_remesh* p, int64_t* edges, void* stream) {
+  SG_REQUIRE(p != nullptr, "sg_remesh_crease_edges: null plan");
+  return remesh_crease_edges(p, edges, (hipStream_t)stream);
+}
+
+SG_API int sg_crease_step(const float* in, float* out, const int64_t* crease_nbr, int64_t V, void* stream) {
+  SG_REQUIRE(V >= 0, "sg_crease_step: negative size (V = %lld)", (long long)V);
+  SG_REQUIRE(V == 0 || (in && out && crease_nbr), "sg_crease_step: null pointer");
+  SG_REQUIRE(V == 0 || in != out, "sg_crease_step: a Jacobi step cannot run in place");
+  return crease_step(in, out, crease_nbr, V, (hipStream_t)stream);
+}
+
 SG_API int sg_mesh_loss_bwd_det(const float* pos, const int64_t* faces, const float* target_pos, const float* v_keep,
                                 const float* target_fn, const float* f_keep, const float* g, int64_t V, int64_t V_ext,
                                 int64_t F, const sg_pool* incidence, float* corner_scratch, float* grad_pos, void* stream_) {

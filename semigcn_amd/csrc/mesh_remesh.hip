@@ -27,6 +27,11 @@
 //              at r; two exclusive scans over the keep flags; the compaction writes vs / par / tri / border into second
 //              buffers (stable), which are then swapped in, and composes the vertex maps of the call.  A collapse reads and
 //              writes only inside its footprint, so footprint-disjoint winners are independent.
+//   creases    with sg_remesh_set_feature on, one more pass per analysis: one lane per interior edge compares the two face
+//              normals with the feature angle (float64 products, no root, no epsilon), flags the edge at the head of its run
+//              and counts it at both ends (integer atomicAdd / atomicMin / atomicMax).  A flagged edge is no flip candidate;
+//              the collapse keeps the end the creases choose, never removes a corner, and removes a crease-line vertex only
+//              along its crease and only forwards.  Off, no launch is added and the kernels see null pointers.
 //
 // hash is the 32-bit mixer x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16: a bijection, so two
 // edges never tie and the order in which the atomics arrive cannot matter.  There are no float atomics; integer max and
@@ -69,6 +74,13 @@ struct sg_remesh {
   sg::GrowBuf<float> vs2;
   sg::GrowBuf<uint8_t> border2;
   int64_t map_before = -1, map_after = -1;          // sizes of the maps; -1: no collapse call yet, both are the identity
+  // creases (sg_remesh_set_feature): with `feat` every analysis flags the crease edges at the heads of their runs and, per
+  // vertex, counts them (nc) and keeps the smallest and the largest crease neighbour (clo, chi)
+  bool feat = false;
+  double cos_t = 0.0;
+  sg::GrowBuf<uint8_t> crease;                      // [3 F]
+  sg::GrowBuf<int32_t> nc, clo, chi;                // [V]
+  int64_t feat_C = -1;                              // crease edges of the last sg_remesh_features; -1: the analysis moved on
 };
 
 namespace sg {
@@ -338,15 +350,99 @@ __device__ inline void flip_quad(const int32_t* __restrict__ vals, const int32_t
   q[3] = tri[3 * f1 + next3(next3(k1))];
 }
 
-// cand[p] = gain << 32 | hash(rank) for a candidate, 0 otherwise; every candidate bids for its four vertices
-__global__ void flip_candidates(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals, const int32_t* __restrict__ head,
+// ---- creases --------------------------------------------------------------------------------------------------------------
+// crease[p] = 1 at the head of an edge with two faces whose normals n1 = n(a, b, c), n2 = n(b, a, d) turn by more than the
+// feature angle: dd = n1 . n2, q = (n1 . n1) (n2 . n2), c2 = cos_t^2; dd < 0 || dd dd < c2 q for cos_t >= 0, dd < 0 && dd dd > c2 q
+// otherwise.  Per end: nc counts the crease edges, clo / chi keep the smallest / largest crease neighbour (integer atomics).
+__global__ void crease_pass(const int32_t* __restrict__ vals, const int32_t* __restrict__ head, int64_t n,
+                            const int32_t* __restrict__ tri, const float* __restrict__ vs, double cos_t,
+                            uint8_t* __restrict__ crease, int32_t* __restrict__ nc, int32_t* __restrict__ clo,
+                            int32_t* __restrict__ chi) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  bool flag = false;
+  if (head[p] && run_length(head, p, n) == 2) {
+    int32_t q4[4];
+    flip_quad(vals, tri, p, q4);
+    const int32_t a = q4[0], b = q4[1], c = q4[2], d = q4[3];
+    const D3 n1 = cross3(sub3(vs, b, a), sub3(vs, c, a)), n2 = cross3(sub3(vs, a, b), sub3(vs, d, b));
+    const double dd = dot3(n1, n2), q = dot3(n1, n1) * dot3(n2, n2), c2 = cos_t * cos_t;
+    flag = cos_t >= 0.0 ? (dd < 0.0 || dd * dd < c2 * q) : (dd < 0.0 && dd * dd > c2 * q);
+    if (flag) {
+      atomicAdd(nc + a, 1);
+      atomicAdd(nc + b, 1);
+      atomicMin(clo + a, b);
+      atomicMax(chi + a, b);
+      atomicMin(clo + b, a);
+      atomicMax(chi + b, a);
+    }
+  }
+  crease[p] = flag ? 1 : 0;
+}
+
+// flag_a[p] = crease[p] (entry n is 0): what the scan of sg_remesh_features numbers
+__global__ void crease_flags(const uint8_t* __restrict__ crease, int64_t n, int32_t* __restrict__ flag_a) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p <= n) flag_a[p] = p < n ? (int32_t)crease[p] : 0;
+}
+
+__global__ void store_crease_total(const int32_t* __restrict__ scan_a, int64_t n, unsigned long long* __restrict__ ctr) {
+  ctr[kTotalA] = (unsigned long long)scan_a[n];
+}
+
+// vclass: 0 smooth, 1 crease-line, 2 corner, 3 border; nbr = (lo, hi) of a crease-line vertex, (-1, -1) otherwise.  nc == null:
+// the feature setting is off and every vertex is smooth or border.
+__global__ void vertex_classes(const uint8_t* __restrict__ border, const int32_t* __restrict__ nc, const int32_t* __restrict__ clo,
+                               const int32_t* __restrict__ chi, int64_t V, uint8_t* __restrict__ vclass, int64_t* __restrict__ nbr) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  const int c = nc ? nc[v] : 0;
+  const uint8_t cls = border[v] ? 3 : (c == 0 ? 0 : (c == 2 ? 1 : 2));
+  vclass[v] = cls;
+  nbr[2 * v] = cls == 1 ? (int64_t)clo[v] : -1;
+  nbr[2 * v + 1] = cls == 1 ? (int64_t)chi[v] : -1;
+}
+
+// the s-th crease edge in ascending (lo, hi): the key of its run
+__global__ void emit_crease_edges(const uint8_t* __restrict__ crease, const int32_t* __restrict__ scan_a,
+                                  const uint64_t* __restrict__ keys, int64_t n, int64_t V, int64_t C, int64_t* __restrict__ edges) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n || !crease[p]) return;
+  const int64_t s = scan_a[p];
+  if (s < 0 || s >= C) return;
+  edges[2 * s] = (int64_t)(keys[p] / (uint64_t)V);
+  edges[2 * s + 1] = (int64_t)(keys[p] % (uint64_t)V);
+}
+
+// One Jacobi step along the creases: a vertex with nbr = (lo, hi) becomes (in[v] + in[lo] + in[hi]) / 3 per component, float32,
+// summed in that order -- mesh_smooth.hip's step for a border vertex with two border edges; every other vertex is copied.
+__global__ void crease_step_kernel(const float* __restrict__ in, const int64_t* __restrict__ nbr, int64_t V, float* __restrict__ out) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  const int64_t lo = nbr[2 * v], hi = nbr[2 * v + 1];
+  const bool move = lo >= 0 && lo < V && hi >= 0 && hi < V;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    float x = in[3 * v + i];
+    if (move) {
+      x += in[3 * lo + i];
+      x += in[3 * hi + i];
+      x = __fdiv_rn(x, 3.f);
+    }
+    out[3 * v + i] = x;
+  }
+}
+
+// cand[p] = gain << 32 | hash(rank) for a candidate, 0 otherwise; every candidate bids for its four vertices.  crease (null:
+// the feature setting is off): a crease edge is no candidate.
+__global__ void flip_candidates(const uint8_t* __restrict__ crease,const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals, const int32_t* __restrict__ head,
                                 const int32_t* __restrict__ incl, int64_t n, int64_t V, const int32_t* __restrict__ tri,
                                 const float* __restrict__ vs, const int32_t* __restrict__ val, const uint8_t* __restrict__ border,
                                 unsigned long long* __restrict__ cand, unsigned long long* __restrict__ slot) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
   unsigned long long key = 0;
-  if (head[p] && run_length(head, p, n) == 2) {
+  if (head[p] && run_length(head, p, n) == 2 && !(crease && crease[p])) {
     int32_t q[4];
     flip_quad(vals, tri, p, q);
     const int32_t a = q[0], b = q[1], c = q[2], d = q[3];
@@ -432,15 +528,22 @@ __device__ inline bool has_edge(const uint64_t* __restrict__ keys, int64_t n, in
 }
 
 // the interior edge whose run starts at p: the kept vertex k, the removed vertex r and the half-edge from r to k; false when
-// both ends are border vertices
+// both ends are border vertices.  nc (null: the feature setting is off) are the crease counts: without a border end the end
+// with a crease is kept when exactly one has one, else the corner end (nc not 2) when exactly one is a corner.
 __device__ inline bool collapse_ends(const int32_t* __restrict__ vals, const int32_t* __restrict__ tri,
-                                     const uint8_t* __restrict__ border, int64_t p, int32_t& k, int32_t& r, int32_t& hs) {
+                                     const uint8_t* __restrict__ border, const int32_t* __restrict__ nc, int64_t p, int32_t& k,
+                                     int32_t& r, int32_t& hs) {
   const int32_t h0 = vals[p], h1 = vals[p + 1];
   const int64_t f0 = h0 / 3;
   const int32_t a = tri[h0], b = tri[3 * f0 + next3((int)(h0 - 3 * f0))];
   const bool ba = border[a] != 0, bb = border[b] != 0;
   if (ba && bb) return false;
   k = ba ? a : (bb ? b : (a < b ? a : b));
+  if (nc && !ba && !bb) {
+    const int na = nc[a], nb = nc[b];
+    if ((na > 0) != (nb > 0)) k = na > 0 ? a : b;
+    else if (na > 0 && (na != 2) != (nb != 2)) k = na != 2 ? a : b;
+  }
   r = k == a ? b : a;
   hs = r == a ? h0 : h1;                              // h0 runs from a to b, h1 from b to a: the mesh was validated
   return true;
@@ -467,7 +570,9 @@ __global__ void collapse_candidates(const uint64_t* __restrict__ keys, const int
                                     const int32_t* __restrict__ head, const int32_t* __restrict__ incl,
                                     const int32_t* __restrict__ twin, int64_t n, int64_t V, const int32_t* __restrict__ tri,
                                     const float* __restrict__ vs, const int32_t* __restrict__ val,
-                                    const uint8_t* __restrict__ border, float lo2, float thr2,
+                                    const uint8_t* __restrict__ border, const uint8_t* __restrict__ crease,
+                                    const int32_t* __restrict__ nc, const int32_t* __restrict__ clo,
+                                    const int32_t* __restrict__ chi, float lo2, float thr2,
                                     unsigned long long* __restrict__ cand, unsigned long long* __restrict__ slot,
                                     unsigned long long* __restrict__ ctr) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -481,8 +586,15 @@ __global__ void collapse_candidates(const uint64_t* __restrict__ keys, const int
     int32_t k = 0, r = 0, hs = 0;
     if (l2 < lo2) {
       atomicAdd(&ctr[kShort], 1ull);
-      bool ok = run_length(head, p, n) == 2 && collapse_ends(vals, tri, border, p, k, r, hs);
+      bool ok = run_length(head, p, n) == 2 && collapse_ends(vals, tri, border, nc, p, k, r, hs);
       int vr = 0;
+      if (ok && nc && nc[r] != 0) {                    // a corner stays; a crease-line vertex leaves along its crease, forwards
+        ok = nc[r] == 2 && crease[p];
+        if (ok) {
+          const int32_t w2 = clo[r] == k ? chi[r] : clo[r];
+          ok = dot3(sub3(vs, r, k), sub3(vs, w2, r)) > 0.0;
+        }
+      }
       if (ok) {
         const int32_t h1 = vals[p + 1];
         const int64_t f1 = h1 / 3;
@@ -529,14 +641,15 @@ __global__ void collapse_candidates(const uint64_t* __restrict__ keys, const int
 
 __global__ void collapse_check(const unsigned long long* __restrict__ cand, const int32_t* __restrict__ vals,
                                const int32_t* __restrict__ twin, const int32_t* __restrict__ tri, const int32_t* __restrict__ val,
-                               const uint8_t* __restrict__ border, const unsigned long long* __restrict__ slot, int64_t n,
-                               uint8_t* __restrict__ win, unsigned long long* __restrict__ ctr) {
+                               const uint8_t* __restrict__ border, const int32_t* __restrict__ nc,
+                               const unsigned long long* __restrict__ slot, int64_t n, uint8_t* __restrict__ win,
+                               unsigned long long* __restrict__ ctr) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
   const unsigned long long key = cand[p];
   uint8_t w8 = 0;
   int32_t k, r, hs;
-  if (key && collapse_ends(vals, tri, border, p, k, r, hs)) {
+  if (key && collapse_ends(vals, tri, border, nc, p, k, r, hs)) {
     bool all = slot[r] == key;
     const int vr = val[r];
     int32_t h = hs;
@@ -559,13 +672,13 @@ __global__ void fill_ones(int32_t* __restrict__ flag, int64_t n) {       // flag
 
 // per winner: its two faces and r are dropped, dest[r] = k, and k goes into r's slot of the other faces at r
 __global__ void collapse_apply(const uint8_t* __restrict__ win, const int32_t* __restrict__ vals, const int32_t* __restrict__ twin,
-                               const int32_t* __restrict__ val, const uint8_t* __restrict__ border, int64_t n, int64_t F,
-                               int32_t* __restrict__ tri, int32_t* __restrict__ flag_f, int32_t* __restrict__ flag_v,
-                               int32_t* __restrict__ dest) {
+                               const int32_t* __restrict__ val, const uint8_t* __restrict__ border,
+                               const int32_t* __restrict__ nc, int64_t n, int64_t F, int32_t* __restrict__ tri,
+                               int32_t* __restrict__ flag_f, int32_t* __restrict__ flag_v, int32_t* __restrict__ dest) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n || !win[p]) return;
   int32_t k, r, hs;
-  if (!collapse_ends(vals, tri, border, p, k, r, hs)) return;
+  if (!collapse_ends(vals, tri, border, nc, p, k, r, hs)) return;
   flag_v[r] = 0;
   dest[r] = k;
   const int vr = val[r];
@@ -644,6 +757,12 @@ int analyse(sg_remesh* s, bool with_valence, hipStream_t stream, bool with_twin 
   if (int rc = s->val.reserve(V, false, stream)) return rc;
   if (with_twin)
     if (int rc = s->twin.reserve(n, false, stream)) return rc;
+  s->feat_C = -1;
+  if (s->feat) {
+    if (int rc = s->crease.reserve(n, false, stream)) return rc;
+    for (auto* b : {&s->nc, &s->clo, &s->chi})
+      if (int rc = b->reserve(V, false, stream)) return rc;
+  }
   const int bits = bits_for((uint64_t)V * (uint64_t)V, 62);    // the keys are below V * V < 2^62
   const int32_t *head = s->head.p, *flag_a = s->flag_a.p, *flag_f = s->flag_f.p;   // hipCUB's iterator arguments keep their const
   size_t tb_sort = 0, tb_incl = 0, tb_a = 0, tb_f = 0;
@@ -672,6 +791,14 @@ int analyse(sg_remesh* s, bool with_valence, hipStream_t stream, bool with_twin 
                                                    s->he_rank.p, s->border.p, with_valence ? s->val.p : nullptr,
                                                    with_twin ? s->twin.p : nullptr, s->ctr.p);
   SG_HIP_TRY(hipGetLastError());
+  if (s->feat) {                                     // the creases of the positions the round starts with
+    SG_HIP_TRY(hipMemsetAsync(s->nc.p, 0, (size_t)V * sizeof(int32_t), stream));
+    SG_HIP_TRY(hipMemsetAsync(s->clo.p, 0x7f, (size_t)V * sizeof(int32_t), stream));   // above every vertex id
+    SG_HIP_TRY(hipMemsetAsync(s->chi.p, 0xff, (size_t)V * sizeof(int32_t), stream));   // -1
+    crease_pass<<<blocks_for(n), kThreads, 0, stream>>>(s->vals_b.p, s->head.p, n, s->tri.p, s->vs.p, s->cos_t, s->crease.p,
+                                                       s->nc.p, s->clo.p, s->chi.p);
+    SG_HIP_TRY(hipGetLastError());
+  }
   return SG_OK;
 }
 
@@ -800,7 +927,7 @@ int remesh_flip(sg_remesh* s, int64_t max_rounds, hipStream_t stream, int64_t* c
     if (int rc = analyse(s, true, stream)) return rc;
     SG_HIP_TRY(hipMemsetAsync(s->slot.p, 0, (size_t)V * sizeof(uint64_t), stream));
     valence_deviation<<<blocks_for(V), kThreads, 0, stream>>>(s->val.p, s->border.p, V, s->ctr.p);
-    flip_candidates<<<blocks_for(n), kThreads, 0, stream>>>(s->keys_b.p, s->vals_b.p, s->head.p, s->incl.p, n, V, s->tri.p,
+    flip_candidates<<<blocks_for(n), kThreads, 0, stream>>>(s->feat ? s->crease.p : nullptr, s->keys_b.p,s->vals_b.p, s->head.p, s->incl.p, n, V, s->tri.p,
                                                            s->vs.p, s->val.p, s->border.p, s->cand.p, s->slot.p);
     flip_check<<<blocks_for(n), kThreads, 0, stream>>>(s->cand.p, s->vals_b.p, s->tri.p, s->slot.p, n, s->win.p, s->ctr.p);
     SG_HIP_TRY(hipGetLastError());
@@ -849,12 +976,13 @@ int remesh_collapse(sg_remesh* s, float lo2, float thr2, int64_t max_rounds, hip
       break;
     }
     if (int rc = analyse(s, true, stream, true)) return rc;
+    const int32_t* nc = s->feat ? s->nc.p : nullptr;  // the analysis may have grown the buffer
     SG_HIP_TRY(hipMemsetAsync(s->slot.p, 0, (size_t)V * sizeof(uint64_t), stream));
     collapse_candidates<<<blocks_for(n), kThreads, 0, stream>>>(s->keys_b.p, s->vals_b.p, s->head.p, s->incl.p, s->twin.p, n, V,
-                                                               s->tri.p, s->vs.p, s->val.p, s->border.p, lo2, thr2, s->cand.p,
-                                                               s->slot.p, s->ctr.p);
+                                                               s->tri.p, s->vs.p, s->val.p, s->border.p, s->crease.p, nc, s->clo.p,
+                                                               s->chi.p, lo2, thr2, s->cand.p, s->slot.p, s->ctr.p);
     collapse_check<<<blocks_for(n), kThreads, 0, stream>>>(s->cand.p, s->vals_b.p, s->twin.p, s->tri.p, s->val.p, s->border.p,
-                                                          s->slot.p, n, s->win.p, s->ctr.p);
+                                                          nc, s->slot.p, n, s->win.p, s->ctr.p);
     SG_HIP_TRY(hipGetLastError());
     unsigned long long c[kCounters];
     if (int rc = read_counters(s, c, stream)) return rc;       // the round's one synchronisation: count -> apply
@@ -877,7 +1005,7 @@ int remesh_collapse(sg_remesh* s, float lo2, float thr2, int64_t max_rounds, hip
     if (int rc = s->temp.reserve(tb_v ? tb_v : 16, false, stream)) return rc;
     fill_ones<<<blocks_for(V + 1), kThreads, 0, stream>>>(s->flag_v.p, V);
     fill_ones<<<blocks_for(F + 1), kThreads, 0, stream>>>(s->flag_f.p, F);
-    collapse_apply<<<blocks_for(n), kThreads, 0, stream>>>(s->win.p, s->vals_b.p, s->twin.p, s->val.p, s->border.p, n, F,
+    collapse_apply<<<blocks_for(n), kThreads, 0, stream>>>(s->win.p, s->vals_b.p, s->twin.p, s->val.p, s->border.p, nc, n, F,
                                                           s->tri.p, s->flag_f.p, s->flag_v.p, s->dest.p);
     SG_HIP_TRY(hipGetLastError());
     size_t tb = s->temp.cap;
@@ -929,6 +1057,68 @@ int remesh_export(const sg_remesh* s, float* vs, int64_t* faces, int64_t* parent
     if (border) SG_HIP_TRY(hipMemcpyAsync(border, s->border.p, (size_t)V, hipMemcpyDeviceToDevice, stream));
   }
   if (F > 0) widen32<<<blocks_for(3 * F), kThreads, 0, stream>>>(s->tri.p, 3 * F, faces);
+  SG_HIP_TRY(hipGetLastError());
+  return SG_OK;
+}
+
+void remesh_set_feature(sg_remesh* s, bool enabled, double cos_t) {
+  s->feat = enabled;
+  s->cos_t = enabled ? cos_t : 0.0;
+  s->feat_C = -1;
+}
+
+int remesh_features(sg_remesh* s, hipStream_t stream, uint8_t* vclass, int64_t* crease_nbr, int64_t* n_crease) {
+  *n_crease = 0;
+  s->feat_C = -1;
+  SG_REQUIRE(s->valid, "sg_remesh_features: the mesh did not pass validation (sg_remesh_query)");
+  const int64_t V = s->V, F = s->F, n = 3 * F;
+  if (V == 0) {                                     // nothing to write, no device to ask
+    s->feat_C = 0;
+    return SG_OK;
+  }
+  SG_REQUIRE(vclass && crease_nbr, "sg_remesh_features: null pointer");
+  int64_t C = 0;
+  if (F == 0) {
+    SG_HIP_TRY(hipMemsetAsync(s->border.p, 0, (size_t)V, stream));
+    vertex_classes<<<blocks_for(V), kThreads, 0, stream>>>(s->border.p, nullptr, nullptr, nullptr, V, vclass, crease_nbr);
+    SG_HIP_TRY(hipGetLastError());
+  } else {
+    if (int rc = analyse(s, false, stream)) return rc;
+    if (s->feat) {
+      crease_flags<<<blocks_for(n + 1), kThreads, 0, stream>>>(s->crease.p, n, s->flag_a.p);
+      SG_HIP_TRY(hipGetLastError());
+      const int32_t* flag_a = s->flag_a.p;           // hipCUB's iterator arguments keep their const
+      size_t tb = s->temp.cap;
+      SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->temp.p, tb, flag_a, s->scan_a.p, (int)(n + 1), stream));
+      store_crease_total<<<1, 1, 0, stream>>>(s->scan_a.p, n, s->ctr.p);
+    }
+    vertex_classes<<<blocks_for(V), kThreads, 0, stream>>>(s->border.p, s->feat ? s->nc.p : nullptr, s->clo.p, s->chi.p, V, vclass,
+                                                          crease_nbr);
+    SG_HIP_TRY(hipGetLastError());
+    if (s->feat) {
+      unsigned long long c[kCounters];
+      if (int rc = read_counters(s, c, stream)) return rc;     // the one synchronisation: the caller sizes the edge list
+      C = (int64_t)c[kTotalA];
+      SG_REQUIRE(C >= 0 && C <= n, "sg_remesh_features: crease count %lld out of range", (long long)C);
+    }
+  }
+  s->feat_C = *n_crease = C;
+  return SG_OK;
+}
+
+int remesh_crease_edges(const sg_remesh* s, int64_t* edges, hipStream_t stream) {
+  SG_REQUIRE(s->feat_C >= 0, "sg_remesh_crease_edges: call sg_remesh_features first (no operation in between)");
+  if (s->feat_C == 0) return SG_OK;
+  SG_REQUIRE(edges != nullptr, "sg_remesh_crease_edges: null pointer");
+  const int64_t n = 3 * s->F;
+  emit_crease_edges<<<blocks_for(n), kThreads, 0, stream>>>(s->crease.p, s->scan_a.p, s->keys_b.p, n, s->V, s->feat_C, edges);
+  SG_HIP_TRY(hipGetLastError());
+  return SG_OK;
+}
+
+int crease_step(const float* in, float* out, const int64_t* crease_nbr, int64_t V, hipStream_t stream) {
+  if (V == 0) return SG_OK;
+  crease_step_kernel<<<blocks_for(V), kThreads, 0, stream>>>(in, crease_nbr, V, out);
   SG_HIP_TRY(hipGetLastError());
   return SG_OK;
 }

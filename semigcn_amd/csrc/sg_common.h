@@ -401,6 +401,10 @@ int remesh_collapse(sg_remesh* s, float lo2, float thr2, int64_t max_rounds, hip
                     int64_t* n_rounds, int64_t* n_short);
 int remesh_collapse_maps(const sg_remesh* s, int64_t* vertex_ids, int64_t* merged_into, hipStream_t stream);
 int remesh_export(const sg_remesh* s, float* vs, int64_t* faces, int64_t* parents, uint8_t* border, hipStream_t stream);
+void remesh_set_feature(sg_remesh* s, bool enabled, double cos_t);
+int remesh_features(sg_remesh* s, hipStream_t stream, uint8_t* vclass, int64_t* crease_nbr, int64_t* n_crease);
+int remesh_crease_edges(const sg_remesh* s, int64_t* edges, hipStream_t stream);
+int crease_step(const float* in, float* out, const int64_t* crease_nbr, int64_t V, hipStream_t stream);
 
 // trace.hip -- optional per-launch event timing (sg_trace_*)
 extern std::atomic<bool> g_trace_on;

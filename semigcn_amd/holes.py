@@ -4,7 +4,8 @@ Replaces the hole-closing part of ``MeshFix.repair()`` in the reference's prepro
 creates the vertices the network exists to place.  Keeping the largest component, which MeshFix does first, is
 ``components.keep_components``; removing self-intersecting triangles, which it does last, is
 ``repair.remove_self_intersections``.  The isotropic remesh of the whole surface that follows
-(preprocess/prepare.py:35-42) is ``remesh.refine_mesh`` (``collapse=True`` for its edge collapse).  MeshFix is
+(preprocess/prepare.py:35-42) is ``remesh.refine_mesh`` (``collapse=True`` for its edge collapse, ``feature_angle=30`` for
+MeshLab's crease angle: sharp edges and corners of a ``-CAD`` input are kept).  MeshFix is
 not available to compare against; the construction below is this module's own and is the specification the tests pin
 (tests/holes_oracle.py restates it in numpy / float64).  The kernels are csrc/mesh_fill.hip; the fairing is
 ``prepare.laplacian_smooth`` (csrc/mesh_smooth.hip) with only the inserted vertices movable.

@@ -240,6 +240,31 @@ def octahedron_sphere(level: int, seed: int = 314) -> SynthMesh:
     return SynthMesh(0, 0, vs, faces, edges, edge_index, z1, x_pos, v_mask)
 
 
+def box_mesh(n: int):
+    """The unit cube with an ``n`` x ``n`` grid of quads on every face, two triangles per quad, the vertices on the cube's
+    edges and corners shared, normals outward: ``(vs float32 [6 n^2 + 2, 3], faces int64 [12 n^2, 3])``.  Twelve straight
+    creases and eight corners: the creased workload beside ``torus_mesh``."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"box_mesh: n must be >= 1, got {n}")
+    i, j = (x.reshape(-1) for x in np.meshgrid(np.arange(n), np.arange(n), indexing="ij"))
+    tris = []
+    for axis in range(3):
+        u, v = (axis + 1) % 3, (axis + 2) % 3             # e_u x e_v = e_axis
+        for side in (0, n):
+            def corner(du, dv):
+                p = np.zeros((n * n, 3), np.int64)
+                p[:, axis], p[:, u], p[:, v] = side, i + du, j + dv
+                return p
+            q = [corner(0, 0), corner(1, 0), corner(1, 1), corner(0, 1)]
+            order = ((0, 1, 2), (0, 2, 3)) if side else ((0, 2, 1), (0, 3, 2))
+            tris += [np.stack([q[a], q[b], q[c]], 1) for a, b, c in order]
+    pts = np.concatenate(tris).reshape(-1, 3)                # lattice points, one per face corner
+    key, inv = np.unique((pts[:, 0] * (n + 1) + pts[:, 1]) * (n + 1) + pts[:, 2], return_inverse=True)
+    vs = np.stack([key // ((n + 1) * (n + 1)), key // (n + 1) % (n + 1), key % (n + 1)], 1) / float(n)
+    return vs.astype(np.float32), inv.reshape(-1, 3).astype(np.int64)
+
+
 def write_obj(path: str, vs, faces=None) -> None:
     """``mesh_common.write_obj`` (OBJ in the dialect util/mesh.py:35-58 parses); looked up when called, since that module
     needs torch and this one does not."""
