@@ -507,6 +507,47 @@ SG_API int sg_parts_emit(sg_parts* p, const float* vs, float* new_vs, int64_t* n
                          void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Making a raw triangle list manifold (csrc/mesh_manifold.hip) -- what
+ * MeshFix.repair() (preprocess/prepare.py:28-33) does before it selects, fills
+ * and repairs: weld coincident vertices, drop degenerate and duplicate faces,
+ * cut non-manifold edges and bow-tie vertices apart, orient the faces, turn
+ * closed components outward.  The rules are specified in
+ * semigcn_amd/manifold.py.
+ *
+ * sg_manifold_create: runs the steps that flags selects on vs float32 [V,3]
+ *   and faces int64 [F,3] and keeps the result.  SG_MANIFOLD_WELD, _DEDUP and
+ *   _CUT need _DROP (degenerate faces and unused vertices go, vertices are
+ *   renumbered); _OUTWARD needs _ORIENT.  Without _DROP no face and no vertex is
+ *   dropped or renumbered.  vs may be null without _WELD and _OUTWARD.  A vertex
+ *   index outside [0, V), 3 F >= 2^31 or V >= 2^31 gives SG_ERR_INVALID.
+ *   F = 0 is valid and asks for no device (V' = 0 with _DROP, else V).
+ *   Synchronises the stream.
+ * sg_manifold_query: info[16] (host) = V, F, V', F', flags, welded vertices,
+ *   degenerate faces, duplicate faces, edges with three or more faces, split
+ *   vertices, flipped faces, non-orientable components, components, components
+ *   with two faces on every edge, 0, 0.
+ * sg_manifold_export: writes to device arrays of the caller new_vs float32
+ *   [V',3] (rows of vs bit for bit), new_faces int64 [F',3], vertex_map int64
+ *   [V] (old to weld representative), vertex_ids int64 [V'] (new to old),
+ *   face_ids int64 [F'] (new to old, ascending), flipped and nonorientable
+ *   uint8 [F'].  new_vs, vertex_map and vertex_ids may be null (not written).
+ *   Writes nothing when F = 0.  Asynchronous.
+ * ------------------------------------------------------------------------- */
+#define SG_MANIFOLD_WELD 1
+#define SG_MANIFOLD_DEDUP 2
+#define SG_MANIFOLD_CUT 4
+#define SG_MANIFOLD_ORIENT 8
+#define SG_MANIFOLD_OUTWARD 16
+#define SG_MANIFOLD_DROP 32
+typedef struct sg_manifold sg_manifold;
+SG_API int sg_manifold_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, int flags, void* stream,
+                              sg_manifold** out);
+SG_API int sg_manifold_destroy(sg_manifold* p);
+SG_API int sg_manifold_query(const sg_manifold* p, int64_t* info);
+SG_API int sg_manifold_export(const sg_manifold* p, const float* vs, float* new_vs, int64_t* new_faces, int64_t* vertex_map,
+                              int64_t* vertex_ids, int64_t* face_ids, uint8_t* flipped, uint8_t* nonorientable, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Refining a mesh to a target edge length (csrc/mesh_remesh.hip): the edge
  * splits, edge collapses and edge flips of the isotropic remesh in the
  * reference's preprocess/prepare.py:35-42.  The rules (priority, selection,

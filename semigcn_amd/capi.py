@@ -218,6 +218,10 @@ _SIGNATURES = {
     "sg_parts_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_parts_select": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
     "sg_parts_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_manifold_create": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, POINTER(c_void_p)]),
+    "sg_manifold_destroy": (c_int, [c_void_p]),
+    "sg_manifold_query": (c_int, [c_void_p, POINTER(c_int64)]),
+    "sg_manifold_export": (c_int, [c_void_p] * 10),
     "sg_remesh_create": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, POINTER(c_void_p)]),
     "sg_remesh_destroy": (c_int, [c_void_p]),
     "sg_remesh_query": (c_int, [c_void_p, POINTER(c_int64)]),
@@ -1646,6 +1650,73 @@ class PartsPlan(_OwnedHandle):
             _check(load().sg_parts_emit(self._h, none_if_empty(vs), none_if_empty(new_vs), none_if_empty(new_faces),
                                         none_if_empty(vertex_ids), none_if_empty(face_ids), _stream(vs)), "sg_parts_emit")
         return new_vs, new_faces, vertex_ids, face_ids
+
+
+class ManifoldPlan(_OwnedHandle):
+    """Owns one sg_manifold (csrc/mesh_manifold.hip): a triangle list welded, cleaned, cut, oriented and turned outward as
+    ``steps`` asks (the rules are specified in semigcn_amd/manifold.py).  Creating it runs the steps; ``export`` hands the
+    result back.  Without ``"drop"`` no face and no vertex is dropped or renumbered."""
+
+    _destroy = "sg_manifold_destroy"
+    _query_fn, _query_len = "sg_manifold_query", 16
+
+    STEPS = {"weld": 1, "dedup": 2, "cut": 4, "orient": 8, "outward": 16, "drop": 32}
+    COUNTS = ("n_welded", "n_degenerate", "n_duplicate_faces", "n_nonmanifold_edges", "n_split_vertices", "n_flipped",
+              "n_nonorientable", "n_components", "n_closed")
+
+    def __init__(self, vs: torch.Tensor, faces: torch.Tensor, steps=("weld", "dedup", "cut", "orient", "outward", "drop")):
+        steps = tuple(steps)
+        for name in steps:
+            if name not in self.STEPS:
+                raise ValueError(f"steps must be among {tuple(self.STEPS)}, got {name!r}")
+        if "drop" not in steps and any(name in steps for name in ("weld", "dedup", "cut")):
+            raise ValueError("steps: 'weld', 'dedup' and 'cut' need 'drop'")
+        if "outward" in steps and "orient" not in steps:
+            raise ValueError("steps: 'outward' needs 'orient'")
+        _require_device(vs, "vs")
+        _require_device(faces, "faces")
+        vs, faces = _vs_arg(vs).detach().contiguous(), _faces_arg(faces)
+        if faces.device != vs.device:
+            raise SemigcnLibraryError(f"faces on {faces.device}, vs on {vs.device}")
+        self.device, self.steps = vs.device, steps
+        self.num_vertices, self.num_faces = vs.shape[0], faces.shape[0]
+        none_if_empty = lambda t: _ptr(t) if t.numel() else None
+        self._create("sg_manifold_create", self.device, none_if_empty(vs), vs.shape[0], none_if_empty(faces), faces.shape[0],
+                     sum(self.STEPS[name] for name in set(steps)), _stream(vs))
+        info = self._query()
+        self.num_new_vertices, self.num_new_faces = int(info[2]), int(info[3])
+        self.counts = {name: int(v) for name, v in zip(self.COUNTS, info[5:14])}
+
+    def export(self, vs: torch.Tensor):
+        """(new_vs float32 [V', 3], new_faces int64 [F', 3], vertex_map int64 [V], vertex_ids int64 [V'], face_ids int64
+        [F'], flipped bool [F'], nonorientable bool [F']) on the plan's device.  Without ``"drop"`` ``new_vs`` is ``vs``
+        itself; with no face at all the maps are the identity (nothing was welded)."""
+        self._open()
+        _require_device(vs, "vs")
+        _vs_arg(vs, self)
+        vs = vs.detach().contiguous()
+        V, Vn, Fn, dev = self.num_vertices, self.num_new_vertices, self.num_new_faces, self.device
+        renumbered = "drop" in self.steps
+        new_faces = torch.empty((Fn, 3), dtype=torch.int64, device=dev)
+        face_ids = torch.empty(Fn, dtype=torch.int64, device=dev)
+        flipped = torch.empty(Fn, dtype=torch.bool, device=dev)
+        nonorientable = torch.empty(Fn, dtype=torch.bool, device=dev)
+        vertex_map = torch.arange(V, dtype=torch.int64, device=dev)
+        if self.num_faces == 0 or not renumbered:
+            new_vs = vs[:Vn]
+            vertex_ids = vertex_map[:Vn]
+        else:
+            new_vs = torch.empty((Vn, 3), dtype=torch.float32, device=dev)
+            vertex_ids = torch.empty(Vn, dtype=torch.int64, device=dev)
+        if self.num_faces:
+            none_if_empty = lambda t: _ptr(t) if t.numel() else None
+            with _on_device(dev):
+                _check(load().sg_manifold_export(self._h, _ptr(vs), none_if_empty(new_vs) if renumbered else None,
+                                                 none_if_empty(new_faces), _ptr(vertex_map) if "weld" in self.steps else None,
+                                                 none_if_empty(vertex_ids) if renumbered else None, none_if_empty(face_ids),
+                                                 none_if_empty(flipped), none_if_empty(nonorientable), _stream(vs)),
+                       "sg_manifold_export")
+        return new_vs, new_faces, vertex_map, vertex_ids, face_ids, flipped, nonorientable
 
 
 class RemeshPlan(_OwnedHandle):

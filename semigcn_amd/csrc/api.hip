@@ -642,6 +642,41 @@ SG_API int sg_parts_emit(sg_parts* p, const float* vs, float* new_vs, int64_t* n
   return parts_emit(p, vs, new_vs, new_faces, vertex_ids, face_ids, (hipStream_t)stream);
 }
 
+// weld, cut and orient a raw triangle list, what MeshFix.repair() does before it selects and fills: csrc/mesh_manifold.hip
+SG_API int sg_manifold_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, int flags, void* stream,
+                              sg_manifold** out) {
+  SG_REQUIRE(out != nullptr, "sg_manifold_create: null out");
+  *out = nullptr;
+  SG_REQUIRE(F >= 0 && V >= 0, "sg_manifold_create: negative size (V = %lld, F = %lld)", (long long)V, (long long)F);
+  const int all = SG_MANIFOLD_WELD | SG_MANIFOLD_DEDUP | SG_MANIFOLD_CUT | SG_MANIFOLD_ORIENT | SG_MANIFOLD_OUTWARD | SG_MANIFOLD_DROP;
+  SG_REQUIRE((flags & ~all) == 0, "sg_manifold_create: unknown flags 0x%x", flags);
+  SG_REQUIRE(!(flags & (SG_MANIFOLD_WELD | SG_MANIFOLD_DEDUP | SG_MANIFOLD_CUT)) || (flags & SG_MANIFOLD_DROP),
+             "sg_manifold_create: flags 0x%x: weld, dedup and cut need SG_MANIFOLD_DROP", flags);
+  SG_REQUIRE(!(flags & SG_MANIFOLD_OUTWARD) || (flags & SG_MANIFOLD_ORIENT),
+             "sg_manifold_create: flags 0x%x: outward needs SG_MANIFOLD_ORIENT", flags);
+  SG_REQUIRE(F == 0 || faces, "sg_manifold_create: null pointer");
+  SG_REQUIRE(F == 0 || V == 0 || vs || !(flags & (SG_MANIFOLD_WELD | SG_MANIFOLD_OUTWARD)), "sg_manifold_create: null pointer");
+  return manifold_create(vs, V, faces, F, flags, (hipStream_t)stream, out);
+}
+
+SG_API int sg_manifold_destroy(sg_manifold* p) {
+  destroy_manifold(p);
+  return SG_OK;
+}
+
+SG_API int sg_manifold_query(const sg_manifold* p, int64_t* info) {
+  SG_REQUIRE(p != nullptr, "sg_manifold_query: null plan");
+  SG_REQUIRE(info != nullptr, "sg_manifold_query: null pointer");
+  manifold_query(p, info);
+  return SG_OK;
+}
+
+SG_API int sg_manifold_export(const sg_manifold* p, const float* vs, float* new_vs, int64_t* new_faces, int64_t* vertex_map,
+                              int64_t* vertex_ids, int64_t* face_ids, uint8_t* flipped, uint8_t* nonorientable, void* stream) {
+  SG_REQUIRE(p != nullptr, "sg_manifold_export: null plan");
+  return manifold_export(p, vs, new_vs, new_faces, vertex_map, vertex_ids, face_ids, flipped, nonorientable, (hipStream_t)stream);
+}
+
 // splitting, collapsing and flipping of the isotropic remesh (preprocess/prepare.py:35-42): csrc/mesh_remesh.hip
 SG_API int sg_remesh_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, void* stream, sg_remesh** out) {
   SG_REQUIRE(out != nullptr, "sg_remesh_create: null out");

@@ -390,6 +390,12 @@ int parts_labels(const sg_parts* s, int64_t* face_label, int64_t* face_count, hi
 int parts_select(sg_parts* s, const uint8_t* keep, hipStream_t stream, int64_t* n_vertices, int64_t* n_faces);
 int parts_emit(sg_parts* s, const float* vs, float* new_vs, int64_t* new_faces, int64_t* vertex_ids, int64_t* face_ids,
                hipStream_t stream);
+// mesh_manifold.hip
+int manifold_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, int flags, hipStream_t stream, sg_manifold** out);
+void destroy_manifold(sg_manifold* s);
+void manifold_query(const sg_manifold* s, int64_t* info);
+int manifold_export(const sg_manifold* s, const float* vs, float* new_vs, int64_t* new_faces, int64_t* vertex_map,
+                    int64_t* vertex_ids, int64_t* face_ids, uint8_t* flipped, uint8_t* nonorientable, hipStream_t stream);
 // mesh_remesh.hip
 int remesh_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, hipStream_t stream, sg_remesh** out);
 void destroy_remesh(sg_remesh* s);

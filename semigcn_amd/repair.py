@@ -52,11 +52,12 @@ Inputs are what ``evaluate`` accepts; HIP device only: a CPU tensor raises ``Sem
 
 Command line::
 
-    python -m semigcn_amd.repair in.obj out.obj [--grow G] [--max-rounds N] [--max-hole-edges N] [--fair-steps K]
+    python -m semigcn_amd.repair in.obj out.obj [--grow G] [--max-rounds N] [--max-hole-edges N] [--fair-steps K] [--manifold]
     python -m semigcn_amd.repair --torus NU NV --fold K [--repeat R] [--out B.obj]
 
 prints one JSON line.  The file form runs ``repair`` and reports ``rounds``, ``removed_per_round``, ``remaining`` and the
-sizes.  ``--torus NU NV --fold K`` runs on ``fold_torus(NU, NV, K)`` and reports the device time (events) of the stages of
+sizes; ``--manifold`` is ``repair(..., make_manifold=True)``.  ``--torus NU NV --fold K`` runs on
+``fold_torus(NU, NV, K)`` and reports the device time (events) of the stages of
 one detection -- ``tree_ms`` (the hierarchy), ``count_ms``, ``scan_ms`` (offsets and the one host read of P),
 ``emit_sort_ms`` -- of the last of ``--repeat`` runs, then ``round_ms``: one full repair round (detect, delete, keep the
 largest component, fill) with the detection that re-checks its result, and ``remaining_after_round``.
@@ -149,8 +150,10 @@ def _grown(faces: torch.Tensor, flagged: torch.Tensor, num_vertices: int, grow: 
     return flagged
 
 
-def _loop(vs, faces, ids, grow, max_rounds, max_hole_edges, fair_steps) -> Repaired:
-    from . import components, holes
+def _loop(vs, faces, ids, grow, max_rounds, max_hole_edges, fair_steps, cut=False) -> Repaired:
+    """``cut``: a deletion may leave two fans hanging on one vertex; cut them apart (``manifold.split_nonmanifold``) before
+    the largest component is taken, so that the boundary can always be ordered into loops."""
+    from . import components, holes, manifold
     rounds, removed = 0, []
     while True:
         hits = self_intersections(vs, faces)
@@ -158,7 +161,11 @@ def _loop(vs, faces, ids, grow, max_rounds, max_hole_edges, fair_steps) -> Repai
             return Repaired(vs, faces, rounds, removed, len(hits), ids)
         drop = _grown(faces, hits.face_mask, vs.shape[0], grow)
         removed.append(int(drop.sum()))
-        kept = components.keep_components((vs, faces[~drop].contiguous()), keep="largest")
+        left = faces[~drop].contiguous()
+        if cut:
+            split = manifold.split_nonmanifold((vs, left))
+            vs, left, ids = split.vs, split.faces, ids[split.vertex_ids]
+        kept = components.keep_components((vs, left), keep="largest")
         ids = ids[kept.vertex_ids]
         if kept.faces.shape[0] == 0:
             vs, faces = kept.vs, kept.faces
@@ -193,22 +200,32 @@ def remove_self_intersections(mesh, grow: int = 1, max_rounds: int = 10, max_hol
 
 
 def repair(mesh, grow: int = 1, max_rounds: int = 10, max_hole_edges: Optional[int] = None,
-           fair_steps: int = prepare.SMOOTH_ITER):
+           fair_steps: int = prepare.SMOOTH_ITER, make_manifold: bool = False):
     """The whole ``MeshFix.repair()`` stage: keep the largest component, close the holes, remove the self-intersections.
     Returns ``(vs, faces, report)``: ``(vs, faces)`` is a valid ``initial`` for ``prepare.prepare_inputs``; ``report`` is
-    the ``Repaired`` of the last step, its ``vertex_ids`` referring to the vertices of ``mesh``."""
-    from . import components, holes
+    the ``Repaired`` of the last step, its ``vertex_ids`` referring to the vertices of ``mesh``.  ``make_manifold``: run
+    ``manifold.make_manifold`` first -- a soup, bow-tie vertices, edges with three faces and disagreeing orientations are
+    then taken instead of refused -- and ``manifold.orient_faces`` once more after the holes are closed, since only then
+    can the kept component be turned outward, and the bow-ties a round's deletion leaves are cut
+    (``manifold.split_nonmanifold``) instead of stopping ``fill_holes``; ``vertex_ids`` then name the weld
+    representatives."""
+    from . import components, holes, manifold
     args = _check_loop_args(grow, max_rounds, max_hole_edges, fair_steps)
     vs, faces = vs_faces(*check_mesh(mesh, dtypes=False))
     with capi._on_device(vs.device):
+        first = manifold.make_manifold((vs, faces)) if make_manifold else None
+        if first is not None:
+            vs, faces = first.vs, first.faces
         kept = components.keep_components((vs, faces), keep="largest")
-        ids = kept.vertex_ids
+        ids = kept.vertex_ids if first is None else first.vertex_ids[kept.vertex_ids]
         vs, faces = kept.vs, kept.faces
         if faces.shape[0]:
             filled = holes.fill_holes((vs, faces), max_hole_edges=max_hole_edges, fair_steps=args[3])
             vs, faces = filled.vs, filled.faces
             ids = torch.cat([ids, ids.new_full((vs.shape[0] - ids.shape[0],), -1)])
-        report = _loop(vs, faces, ids, *args)
+            if first is not None:
+                faces = manifold.orient_faces((vs, faces), outward=True).faces
+        report = _loop(vs, faces, ids, *args, cut=first is not None)
         return report.vs, report.faces, report
 
 
@@ -252,6 +269,7 @@ def main(argv=None) -> int:
     ap.add_argument("--max-rounds", type=int, default=10)
     ap.add_argument("--max-hole-edges", type=int, default=None, help="leave loops with more edges open (default: fill all)")
     ap.add_argument("--fair-steps", type=int, default=prepare.SMOOTH_ITER, help="smoothing steps on the inserted vertices")
+    ap.add_argument("--manifold", action="store_true", help="weld, cut and orient the input first (semigcn_amd.manifold)")
     ap.add_argument("--torus", type=int, nargs=2, metavar=("NU", "NV"), help="time the stages on a synthetic torus")
     ap.add_argument("--fold", type=int, default=0, help="with --torus: the number of patches pushed through the tube")
     ap.add_argument("--repeat", type=int, default=1, help="run the detection this many times and report the last")
@@ -267,7 +285,7 @@ def main(argv=None) -> int:
     kw = dict(grow=args.grow, max_hole_edges=args.max_hole_edges, fair_steps=args.fair_steps)
     if args.scan is not None:
         mesh = read_obj(args.scan)
-        vs, faces, rep = repair(mesh, max_rounds=args.max_rounds, **kw)
+        vs, faces, rep = repair(mesh, max_rounds=args.max_rounds, make_manifold=args.manifold, **kw)
         write_obj(args.out_path, vs, faces)
         print(json.dumps({"n_vertices": int(mesh[0].shape[0]), "n_faces": int(mesh[1].shape[0]),
                           "out_vertices": int(vs.shape[0]), "out_faces": int(faces.shape[0]), "rounds": rep.rounds,
