@@ -583,12 +583,38 @@ SG_API int sg_manifold_export(const sg_manifold* p, const float* vs, float* new_
  *   that collapsed something, *n_short the edges with len2 < lo2 that are left.
  *   Vertices and faces are renumbered (stable compaction); parents are remapped.
  *   One stream synchronisation per round.
- * sg_remesh_collapse_maps: for the last sg_remesh_collapse call, with V_before
+ * sg_remesh_simplify: simplifies the mesh to target_v vertices by rounds of
+ *   quadric edge collapses (semigcn_amd/simplify.py is the specification).  The
+ *   vertex quadrics are computed once, on the mesh the call starts with; a round
+ *   prices every edge with two faces and at most one border end, refuses the
+ *   ones that would change the topology, break a valence floor, fold a face over
+ *   or have no finite cost, admits the min(V - target_v, candidates) cheapest
+ *   (one radix sort of the 64-bit priorities; the cut stays on the device) and
+ *   collapses the admitted ones that hold every vertex of their footprint.
+ *   quadrics_mode: SG_QUADRICS_OWN (the kept vertex keeps its quadric) or
+ *   SG_QUADRICS_SUM (it takes the sum).  counts (host, int64 [3 max_rounds])
+ *   receives (candidates, admitted, winners) of every round that collapsed
+ *   something, *n_rounds their number, *n_refused the refused edges of the last
+ *   round analysed.  Stops at target_v (never below), at a round without a
+ *   winner, or after max_rounds rounds; V > target_v on return is no error.
+ *   Refuses an invalid input and a plan with the crease rules on
+ *   (sg_remesh_set_feature), and then writes nothing.  Vertices and faces are
+ *   renumbered (stable compaction); parents are remapped.  One stream
+ *   synchronisation per round.
+ * sg_remesh_quadrics: writes the vertex quadrics of the mesh as it stands,
+ *   quadrics float64 [V,10] (device): the entries (xx, xy, xz, xw, yy, yz, yw,
+ *   zz, zw, ww) of the sum over the faces at the vertex, in ascending face
+ *   index, of p p^T / (n . n) with n = (b - a) x (c - a), p = (n, -n . a).
+ *   Asynchronous.  V = 0 touches no device.  An sg_remesh_simplify that
+ *   follows with no other call on the plan in between works on these and does
+ *   not compute them again.
+ * sg_remesh_collapse_maps: for the last sg_remesh_collapse or
+ *   sg_remesh_simplify call, whichever ran last, with V_before
  *   and V' the vertex counts before and after it: vertex_ids int64 [V'] (device)
  *   = the index each surviving vertex had before the call, merged_into int64
  *   [V_before] (device) = the index after the call of the vertex that each
  *   earlier vertex ended up in (its own new index when it survived).  Before any
- *   collapse call both are the identity over the current V.  Asynchronous.
+ *   collapse or simplify call both are the identity over the current V.  Asynchronous.
  * sg_remesh_export: writes the current mesh to device arrays of the caller:
  *   vs float32 [V,3], faces int64 [F,3], parents int64 [V,2] ((i, i) for a
  *   vertex of the input, the two ends (lo, hi) of the split edge otherwise) and,
@@ -625,6 +651,10 @@ SG_API int sg_remesh_split(sg_remesh* p, float thr2, int64_t max_rounds, void* s
 SG_API int sg_remesh_flip(sg_remesh* p, int64_t max_rounds, void* stream, int64_t* counts, int64_t* n_rounds, int64_t* deviation);
 SG_API int sg_remesh_collapse(sg_remesh* p, float lo2, float thr2, int64_t max_rounds, void* stream, int64_t* counts,
                               int64_t* n_rounds, int64_t* n_short);
+enum { SG_QUADRICS_OWN = 0, SG_QUADRICS_SUM = 1 };
+SG_API int sg_remesh_simplify(sg_remesh* p, int64_t target_v, int quadrics_mode, int64_t max_rounds, void* stream, int64_t* counts,
+                              int64_t* n_rounds, int64_t* n_refused);
+SG_API int sg_remesh_quadrics(sg_remesh* p, double* quadrics, void* stream);
 SG_API int sg_remesh_collapse_maps(const sg_remesh* p, int64_t* vertex_ids, int64_t* merged_into, void* stream);
 SG_API int sg_remesh_export(const sg_remesh* p, float* vs, int64_t* faces, int64_t* parents, uint8_t* border, void* stream);
 SG_API int sg_remesh_set_feature(sg_remesh* p, int enabled, double cos_t);

@@ -229,6 +229,9 @@ _SIGNATURES = {
     "sg_remesh_flip": (c_int, [c_void_p, c_int64, c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "sg_remesh_collapse": (c_int, [c_void_p, c_float, c_float, c_int64, c_void_p, POINTER(c_int64), POINTER(c_int64),
                                    POINTER(c_int64)]),
+    "sg_remesh_simplify": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, POINTER(c_int64), POINTER(c_int64),
+                                   POINTER(c_int64)]),
+    "sg_remesh_quadrics": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sg_remesh_collapse_maps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_remesh_export": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_remesh_set_feature": (c_int, [c_void_p, c_int, ctypes.c_double]),
@@ -1788,8 +1791,39 @@ class RemeshPlan(_OwnedHandle):
         self._map_sizes = (self.num_vertices, before)
         return [int(c) for c in counts[: n_rounds.value]], int(n_short.value)
 
+    #: ``quadrics`` of ``simplify``: what the kept vertex of a collapse does with its quadric (SG_QUADRICS_OWN / _SUM)
+    QUADRICS = {"own": 0, "sum": 1}
+
+    def simplify(self, target_v: int, quadrics: str = "own", max_rounds: int = 256):
+        """([(candidates, admitted, winners) per round], refused edges of the last round analysed): rounds of quadric edge
+        collapses until ``target_v`` vertices are left, a round has no winner or ``max_rounds`` rounds ran (the rule is
+        specified in semigcn_amd/simplify.py).  Vertices and faces are renumbered; ``collapse_maps`` returns the maps."""
+        self._open()
+        if quadrics not in self.QUADRICS:
+            raise ValueError(f"quadrics must be 'own' or 'sum', got {quadrics!r}")
+        max_rounds = int(max_rounds)
+        counts = (c_int64 * (3 * max(max_rounds, 1)))()
+        n_rounds, n_refused = c_int64(), c_int64()
+        before = self.num_vertices
+        with _on_device(self.device):
+            _check(load().sg_remesh_simplify(self._h, int(target_v), self.QUADRICS[quadrics], max_rounds,
+                                             _raw_stream_of(self.device), counts, byref(n_rounds), byref(n_refused)),
+                   "sg_remesh_simplify")
+        self._sizes()
+        self._map_sizes = (self.num_vertices, before)
+        return [tuple(int(c) for c in counts[3 * i: 3 * i + 3]) for i in range(n_rounds.value)], int(n_refused.value)
+
+    def quadrics(self):
+        """float64 [V, 10]: the vertex quadrics of the mesh as it stands (semigcn_amd/simplify.py, "Quadrics")."""
+        self._open()
+        out = torch.empty((self.num_vertices, 10), dtype=torch.float64, device=self.device)
+        with _on_device(self.device):
+            _check(load().sg_remesh_quadrics(self._h, _ptr(out) if out.numel() else None, _raw_stream_of(self.device)),
+                   "sg_remesh_quadrics")
+        return out
+
     def collapse_maps(self):
-        """(vertex_ids int64 [V'], merged_into int64 [V_before]) of the last ``collapse`` call: the index each surviving
+        """(vertex_ids int64 [V'], merged_into int64 [V_before]) of the last ``collapse`` or ``simplify`` call: the index each surviving
         vertex had before it, and the index after it of the vertex each earlier vertex ended up in.  Both are the identity
         before any ``collapse``."""
         self._open()

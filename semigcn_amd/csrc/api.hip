@@ -730,6 +730,22 @@ SG_API int sg_remesh_collapse_maps(const sg_remesh* p, int64_t* vertex_ids, int6
   return remesh_collapse_maps(p, vertex_ids, merged_into, (hipStream_t)stream);
 }
 
+SG_API int sg_remesh_simplify(sg_remesh* p, int64_t target_v, int quadrics_mode, int64_t max_rounds, void* stream, int64_t* counts,
+                              int64_t* n_rounds, int64_t* n_refused) {
+  SG_REQUIRE(p != nullptr, "sg_remesh_simplify: null plan");
+  SG_REQUIRE(target_v >= 0, "sg_remesh_simplify: negative target_v (%lld)", (long long)target_v);
+  SG_REQUIRE(max_rounds >= 0, "sg_remesh_simplify: negative max_rounds (%lld)", (long long)max_rounds);
+  SG_REQUIRE(quadrics_mode == SG_QUADRICS_OWN || quadrics_mode == SG_QUADRICS_SUM,
+             "sg_remesh_simplify: unknown quadrics_mode %d (SG_QUADRICS_OWN or SG_QUADRICS_SUM)", quadrics_mode);
+  SG_REQUIRE(n_rounds && n_refused && (max_rounds == 0 || counts), "sg_remesh_simplify: null pointer");
+  return remesh_simplify(p, target_v, quadrics_mode, max_rounds, (hipStream_t)stream, counts, n_rounds, n_refused);
+}
+
+SG_API int sg_remesh_quadrics(sg_remesh* p, double* quadrics, void* stream) {
+  SG_REQUIRE(p != nullptr, "sg_remesh_quadrics: null plan");
+  return remesh_quadrics(p, quadrics, (hipStream_t)stream);
+}
+
 SG_API int sg_remesh_export(const sg_remesh* p, float* vs, int64_t* faces, int64_t* parents, uint8_t* border, void* stream) {
   SG_REQUIRE(p != nullptr, "sg_remesh_export: null plan");
   return remesh_export(p, vs, faces, parents, border, (hipStream_t)stream);

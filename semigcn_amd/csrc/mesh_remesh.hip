@@ -32,6 +32,15 @@
 //              and counts it at both ends (integer atomicAdd / atomicMin / atomicMax).  A flagged edge is no flip candidate;
 //              the collapse keeps the end the creases choose, never removes a corner, and removes a crease-line vertex only
 //              along its crease and only forwards.  Off, no launch is added and the kernels see null pointers.
+//   simplify   (semigcn_amd/simplify.py) quadric edge collapse to a vertex budget on the same plan.  Once per call: one stable
+//              sort of the 3 F corners by vertex and one lane per vertex sum the face quadrics p p^T / (n . n) in ascending
+//              face index (float64, ten divisions per face, no root).  A round: the collapse analysis; a price pass, one lane
+//              per interior edge, walks the fans of r and of k, evaluates link, valence floors and the fold-over guard at the
+//              position k will have, and keys the edge (0xFFFFFFFF - bits(float32(cost))) << 32 | hash(rank); one radix sort
+//              of the keys and a one-lane kernel leave the cut of the min(need, candidates) highest in device memory; the bid
+//              pass (64-bit atomicMax over {k, r} + ring(k) + ring(r)) and the check pass read it there; ONE host
+//              synchronisation reads candidates, admitted and winners; the apply and compaction are the collapse's, after k
+//              has moved to the midpoint, and the quadrics are compacted with the vertices.
 //
 // hash is the 32-bit mixer x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16: a bijection, so two
 // edges never tie and the order in which the atomics arrive cannot matter.  There are no float atomics; integer max and
@@ -73,6 +82,8 @@ struct sg_remesh {
   sg::GrowBuf<int32_t> twin, flag_v, scan_v, dest, par2, tri2, ids, ids2, into;
   sg::GrowBuf<float> vs2;
   sg::GrowBuf<uint8_t> border2;
+  sg::GrowBuf<double> quad, quad2;                  // simplify: the vertex quadrics [V][10], and where the compaction writes them
+  bool quad_fresh = false;                          // quad holds the quadrics of the mesh as it stands (sg_remesh_quadrics just ran)
   int64_t map_before = -1, map_after = -1;          // sizes of the maps; -1: no collapse call yet, both are the identity
   // creases (sg_remesh_set_feature): with `feat` every analysis flags the crease edges at the heads of their runs and, per
   // vertex, counts them (nc) and keeps the smallest and the largest crease neighbour (clo, chi)
@@ -738,6 +749,272 @@ __global__ void iota(T* __restrict__ out, int64_t n) {
   if (i < n) out[i] = (T)i;
 }
 
+// ---- simplify -------------------------------------------------------------------------------------------------------------
+// The specification is semigcn_amd/simplify.py.  The counters of a simplify round live in slots the collapse analysis leaves
+// alone: legal candidates, refused edges, the admitted count and the cut.
+enum { kCand = kLong, kRefused = kShort, kAdmitted = kTotalA, kCut = kTotalF };
+
+__global__ void corner_keys(const int32_t* __restrict__ tri, int64_t n, uint64_t* __restrict__ keys, int32_t* __restrict__ vals) {
+  const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (h >= n) return;
+  keys[h] = (uint64_t)(uint32_t)tri[h];
+  vals[h] = (int32_t)h;
+}
+
+// quad[v] = the sum of K = p p^T / (n . n) over the faces at v in ascending face index (the corners were sorted by vertex, stably):
+// ten entries (xx, xy, xz, xw, yy, yz, yw, zz, zw, ww), ten float64 divisions per face, no root
+__global__ void vertex_quadrics(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals, int64_t n, int64_t V,
+                                const int32_t* __restrict__ tri, const float* __restrict__ vs, double* __restrict__ quad) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < (uint64_t)v) lo = mid + 1;
+    else hi = mid;
+  }
+  double q[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int64_t p = lo; p < n && keys[p] == (uint64_t)v; ++p) {
+    const int32_t h = vals[p];
+    if (h < 0 || h >= n) break;
+    const int64_t f = h / 3;
+    const int32_t a = tri[3 * f], b = tri[3 * f + 1], c = tri[3 * f + 2];
+    const D3 nrm = cross3(sub3(vs, b, a), sub3(vs, c, a));
+    const double nn = dot3(nrm, nrm);
+    if (nn == 0.0) continue;
+    const double ax = (double)vs[3 * (int64_t)a], ay = (double)vs[3 * (int64_t)a + 1], az = (double)vs[3 * (int64_t)a + 2];
+    const double pl[4] = {nrm.x, nrm.y, nrm.z, -(nrm.x * ax + nrm.y * ay + nrm.z * az)};
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = i; j < 4; ++j, ++e) q[e] = q[e] + (pl[i] * pl[j]) / nn;
+  }
+#pragma unroll
+  for (int e = 0; e < 10; ++e) quad[10 * v + e] = q[e];
+}
+
+// The faces at v, from the half-edge hs that starts at v: face(x, y) for every face, rotated to read (v, x, y), and vert(u) for
+// every vertex of ring(v), each once -- forwards through twin and next half-edges until the fan closes or ends at a border,
+// then backwards from hs.  At most `limit` faces are visited.  Returns the number of ring vertices seen: val[v] exactly when
+// the faces at v are one fan (closed round an interior vertex, open at a border vertex); -1 when the walk ran out.
+template <class Face, class Vert>
+__device__ inline int walk_ring(const int32_t* __restrict__ tri, const int32_t* __restrict__ twin, int64_t n, int32_t hs, int limit,
+                                Face&& face, Vert&& vert) {
+  int seen = 0, faces = 0;
+  bool closed = false, ended = false;
+  int32_t h = hs;
+  while (faces < limit) {
+    int32_t w, y;
+    const int32_t t = fan_step(tri, twin, n, h, w, y);
+    face(w, y);
+    vert(w);
+    ++faces;
+    ++seen;
+    if (t < 0) {
+      vert(y);
+      ++seen;
+      ended = true;
+      break;
+    }
+    if (t == hs) {
+      closed = true;
+      break;
+    }
+    h = t;
+  }
+  if (closed) return seen;
+  if (!ended) return -1;
+  h = hs;
+  while (faces < limit) {
+    const int32_t t = twin[h];
+    if (t < 0 || t >= n) break;
+    const int64_t f = t / 3;
+    const int j = (int)(t - 3 * f);
+    h = (int32_t)(3 * f + next3(j));                    // t runs from w to v in the face (w, v, z): h runs from v to z
+    const int32_t z = tri[3 * f + next3(next3(j))];
+    face(z, tri[t]);
+    vert(z);
+    ++faces;
+    ++seen;
+  }
+  return seen;
+}
+
+__device__ inline D3 sub3p(const float* __restrict__ vs, int32_t p, const float q[3]) {          // vs[p] - q in float64
+  return {(double)vs[3 * (int64_t)p] - (double)q[0], (double)vs[3 * (int64_t)p + 1] - (double)q[1],
+          (double)vs[3 * (int64_t)p + 2] - (double)q[2]};
+}
+
+// the ends of the candidate at p as collapse_ends names them, and the half-edge from k to r
+__device__ inline bool simplify_ends(const int32_t* __restrict__ vals, const int32_t* __restrict__ tri,
+                                     const uint8_t* __restrict__ border, int64_t p, int32_t& k, int32_t& r, int32_t& hs,
+                                     int32_t& hk) {
+  if (!collapse_ends(vals, tri, border, nullptr, p, k, r, hs)) return false;
+  hk = hs == vals[p] ? vals[p + 1] : vals[p];
+  return true;
+}
+
+// cand[p] = (0xFFFFFFFF - bits(float32(cost))) << 32 | hash(rank) for a legal candidate, 0 otherwise; counts the legal and the
+// refused ones.  Nobody bids here: the cut is not known yet.
+__global__ void simplify_price(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals, const int32_t* __restrict__ head,
+                               const int32_t* __restrict__ incl, const int32_t* __restrict__ twin, int64_t n, int64_t V,
+                               const int32_t* __restrict__ tri, const float* __restrict__ vs, const int32_t* __restrict__ val,
+                               const uint8_t* __restrict__ border, const double* __restrict__ quad,
+                               unsigned long long* __restrict__ cand, unsigned long long* __restrict__ ctr) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  unsigned long long key = 0;
+  int32_t k = 0, r = 0, hs = 0, hk = 0;
+  if (head[p] && run_length(head, p, n) == 2 && simplify_ends(vals, tri, border, p, k, r, hs, hk)) {
+    const int32_t h0 = vals[p], h1 = vals[p + 1];
+    const int64_t f0 = h0 / 3, f1 = h1 / 3;
+    const int32_t c = tri[3 * f0 + next3(next3((int)(h0 - 3 * f0)))], d = tri[3 * f1 + next3(next3((int)(h1 - 3 * f1)))];
+    const int vr = val[r], vk = val[k], vn = vk + vr - 4;
+    const bool moves = border[k] == 0;
+    float P[3];                                        // where k will be
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int64_t lo = k < r ? k : r, hi = k < r ? r : k;
+      P[i] = moves ? (vs[3 * lo + i] + vs[3 * hi + i]) * kHalf : vs[3 * (int64_t)k + i];
+    }
+    bool ok = c != d && val[c] - 1 >= valence_floor(border, c) && val[d] - 1 >= valence_floor(border, d) &&
+              vn >= valence_floor(border, k);
+    if (ok) {                                          // the fan of r: one closed cycle, the link, the guard
+      int links = 0;
+      const int seen = walk_ring(
+          tri, twin, n, hs, vr,
+          [&](int32_t x, int32_t y) {
+            if (x == k || y == k) return;
+            const D3 no = cross3(sub3(vs, x, r), sub3(vs, y, r)), nw = cross3(sub3p(vs, x, P), sub3p(vs, y, P));
+            if (!(dot3(no, nw) > 0.0)) ok = false;
+          },
+          [&](int32_t u) {
+            if (u != k && has_edge(keys, n, V, k, u)) ++links;
+          });
+      ok = ok && seen == vr && links == 2;
+    }
+    if (ok) {                                          // the fan of k: one fan, and the guard when k moves
+      const int seen = walk_ring(
+          tri, twin, n, hk, vk,
+          [&](int32_t x, int32_t y) {
+            if (!moves || x == r || y == r) return;
+            const D3 no = cross3(sub3(vs, x, k), sub3(vs, y, k)), nw = cross3(sub3p(vs, x, P), sub3p(vs, y, P));
+            if (!(dot3(no, nw) > 0.0)) ok = false;
+          },
+          [](int32_t) {});
+      ok = ok && seen == vk;
+    }
+    if (ok) {
+      const double* __restrict__ qk = quad + 10 * (int64_t)k;
+      const double* __restrict__ qr = quad + 10 * (int64_t)r;
+      double q[10];
+#pragma unroll
+      for (int e = 0; e < 10; ++e) q[e] = qk[e] + qr[e];
+      const double x = (double)P[0], y = (double)P[1], z = (double)P[2];
+      const double s0 = q[0] * x + q[1] * y + q[2] * z + q[3];
+      const double s1 = q[1] * x + q[4] * y + q[5] * z + q[6];
+      const double s2 = q[2] * x + q[5] * y + q[7] * z + q[8];
+      const double s3 = q[3] * x + q[6] * y + q[8] * z + q[9];
+      const double err = x * s0 + y * s1 + z * s2 + s3;
+      double pen = (double)(iabs(vn - 6) + 1);
+      if (vn == 3) pen = pen * 100000.0;
+      double cost = err * pen;
+      ok = isfinite(cost);
+      if (ok) {
+        cost = cost > 0.0 ? cost : 0.0;
+        const float c32 = cost > 3.4028234663852886e38 ? 3.4028234663852886e38f : (float)cost;
+        key = ((unsigned long long)(0xFFFFFFFFu - __float_as_uint(c32)) << 32) | hash32((uint32_t)(incl[p] - 1));
+      }
+    }
+    atomicAdd(&ctr[ok ? kCand : kRefused], 1ull);
+  }
+  cand[p] = key;
+}
+
+// sorted = the n keys of the round in ascending order (zeros first).  With C legal candidates the min(need, C) highest bid:
+// the cut is the lowest key among them.
+__global__ void simplify_cut(const unsigned long long* __restrict__ sorted, int64_t n, int64_t need,
+                             unsigned long long* __restrict__ ctr) {
+  const int64_t C = (int64_t)ctr[kCand];
+  int64_t m = need < C ? need : C;
+  if (m < 0 || m > n) m = 0;
+  ctr[kAdmitted] = (unsigned long long)m;
+  ctr[kCut] = m > 0 ? sorted[n - m] : ~0ull;
+}
+
+template <class Fn>
+__device__ inline void simplify_footprint(const int32_t* __restrict__ vals, const int32_t* __restrict__ twin,
+                                          const int32_t* __restrict__ tri, const int32_t* __restrict__ val,
+                                          const uint8_t* __restrict__ border, int64_t n, int64_t p, Fn&& fn) {
+  int32_t k, r, hs, hk;
+  if (!simplify_ends(vals, tri, border, p, k, r, hs, hk)) return;
+  fn(k);
+  fn(r);
+  walk_ring(tri, twin, n, hs, val[r], [](int32_t, int32_t) {}, fn);
+  walk_ring(tri, twin, n, hk, val[k], [](int32_t, int32_t) {}, fn);
+}
+
+// every admitted candidate bids for the vertices of its footprint {k, r} + ring(k) + ring(r)
+__global__ void simplify_bid(const unsigned long long* __restrict__ cand, const int32_t* __restrict__ vals,
+                             const int32_t* __restrict__ twin, const int32_t* __restrict__ tri, const int32_t* __restrict__ val,
+                             const uint8_t* __restrict__ border, const unsigned long long* __restrict__ ctr, int64_t n,
+                             unsigned long long* __restrict__ slot) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const unsigned long long key = cand[p];
+  if (!key || ctr[kAdmitted] == 0 || key < ctr[kCut]) return;
+  simplify_footprint(vals, twin, tri, val, border, n, p, [&](int32_t u) { atomicMax(slot + u, key); });
+}
+
+__global__ void simplify_check(const unsigned long long* __restrict__ cand, const int32_t* __restrict__ vals,
+                               const int32_t* __restrict__ twin, const int32_t* __restrict__ tri, const int32_t* __restrict__ val,
+                               const uint8_t* __restrict__ border, const unsigned long long* __restrict__ slot, int64_t n,
+                               uint8_t* __restrict__ win, unsigned long long* __restrict__ ctr) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const unsigned long long key = cand[p];
+  uint8_t w8 = 0;
+  if (key && ctr[kAdmitted] != 0 && key >= ctr[kCut]) {
+    bool all = true;
+    simplify_footprint(vals, twin, tri, val, border, n, p, [&](int32_t u) {
+      if (slot[u] != key) all = false;
+    });
+    w8 = all ? 1 : 0;
+    if (w8) atomicAdd(&ctr[kWinners], 1ull);
+  }
+  win[p] = w8;
+}
+
+// per winner, before the faces are rewritten: k goes to the midpoint unless it is a border vertex; sum: Q[k] = Q[k] + Q[r]
+__global__ void simplify_move(const uint8_t* __restrict__ win, const int32_t* __restrict__ vals, const int32_t* __restrict__ tri,
+                              const uint8_t* __restrict__ border, int64_t n, int sum, float* __restrict__ vs,
+                              double* __restrict__ quad) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n || !win[p]) return;
+  int32_t k, r, hs;
+  if (!collapse_ends(vals, tri, border, nullptr, p, k, r, hs)) return;
+  if (!border[k]) {
+    const int64_t lo = k < r ? k : r, hi = k < r ? r : k;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) vs[3 * (int64_t)k + i] = (vs[3 * lo + i] + vs[3 * hi + i]) * kHalf;
+  }
+  if (sum) {
+#pragma unroll
+    for (int e = 0; e < 10; ++e) quad[10 * (int64_t)k + e] = quad[10 * (int64_t)k + e] + quad[10 * (int64_t)r + e];
+  }
+}
+
+__global__ void compact_quadrics(const int32_t* __restrict__ flag_v, const int32_t* __restrict__ scan_v, int64_t V, int64_t V2,
+                                 const double* __restrict__ quad, double* __restrict__ quad2) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V || !flag_v[v]) return;
+  const int64_t m = scan_v[v];
+  if (m < 0 || m >= V2) return;
+#pragma unroll
+  for (int e = 0; e < 10; ++e) quad2[10 * m + e] = quad[10 * v + e];
+}
+
 // ---- host -------------------------------------------------------------------------------------------------------------------
 // keys, sort, heads, ranks, edge pass on the mesh as it stands; resets the counters first.  No host synchronisation unless a
 // scratch buffer has to grow.
@@ -758,6 +1035,7 @@ int analyse(sg_remesh* s, bool with_valence, hipStream_t stream, bool with_twin 
   if (with_twin)
     if (int rc = s->twin.reserve(n, false, stream)) return rc;
   s->feat_C = -1;
+  s->quad_fresh = false;                             // whoever analyses is about to change the mesh, or has
   if (s->feat) {
     if (int rc = s->crease.reserve(n, false, stream)) return rc;
     for (auto* b : {&s->nc, &s->clo, &s->chi})
@@ -955,6 +1233,61 @@ void swap_bufs(GrowBuf<T>& a, GrowBuf<T>& b) {
 
 }  // namespace
 
+namespace {
+// The second half of a collapse round, shared by sg_remesh_collapse and sg_remesh_simplify: the W winners in win[] are applied
+// to the mesh of the round's analysis, vertices and faces are compacted (stable) and the maps of the call are composed.
+// quad_mode < 0: no quadrics; 0 / 1 (simplify, "own" / "sum"): the kept vertex of a winner moves first, and the quadrics are
+// compacted with the vertices.
+int apply_and_compact(sg_remesh* s, int64_t W, int64_t V_before, const int32_t* nc, int quad_mode, hipStream_t stream) {
+  const int64_t V = s->V, F = s->F, n = 3 * F;
+  const int64_t V2 = V - W, F2 = F - 2 * W;
+  for (auto* b : {&s->flag_v, &s->scan_v})
+    if (int rc = b->reserve(V + 1, false, stream)) return rc;
+  if (int rc = s->dest.reserve(V, false, stream)) return rc;
+  if (int rc = s->vs2.reserve(3 * V2, false, stream)) return rc;
+  if (int rc = s->par2.reserve(2 * V2, false, stream)) return rc;
+  if (int rc = s->border2.reserve(V2, false, stream)) return rc;
+  if (int rc = s->ids2.reserve(V2, false, stream)) return rc;
+  if (int rc = s->tri2.reserve(3 * F2, false, stream)) return rc;
+  const int32_t *flag_v = s->flag_v.p, *flag_f = s->flag_f.p;   // hipCUB's iterator arguments keep their const
+  size_t tb_v = 0;
+  SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_v, flag_v, s->scan_v.p, (int)(V + 1), stream));
+  if (int rc = s->temp.reserve(tb_v ? tb_v : 16, false, stream)) return rc;
+  fill_ones<<<blocks_for(V + 1), kThreads, 0, stream>>>(s->flag_v.p, V);
+  fill_ones<<<blocks_for(F + 1), kThreads, 0, stream>>>(s->flag_f.p, F);
+  if (quad_mode >= 0) {
+    if (int rc = s->quad2.reserve(10 * V2, false, stream)) return rc;
+    simplify_move<<<blocks_for(n), kThreads, 0, stream>>>(s->win.p, s->vals_b.p, s->tri.p, s->border.p, n, quad_mode, s->vs.p,
+                                                         s->quad.p);
+  }
+  collapse_apply<<<blocks_for(n), kThreads, 0, stream>>>(s->win.p, s->vals_b.p, s->twin.p, s->val.p, s->border.p, nc, n, F,
+                                                        s->tri.p, s->flag_f.p, s->flag_v.p, s->dest.p);
+  SG_HIP_TRY(hipGetLastError());
+  size_t tb = s->temp.cap;
+  SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->temp.p, tb, flag_v, s->scan_v.p, (int)(V + 1), stream));
+  tb = s->temp.cap;
+  SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->temp.p, tb, flag_f, s->scan_f.p, (int)(F + 1), stream));
+  compact_vertices<<<blocks_for(V), kThreads, 0, stream>>>(s->flag_v.p, s->scan_v.p, s->dest.p, V, V2, s->vs.p, s->par.p,
+                                                          s->border.p, s->ids.p, s->vs2.p, s->par2.p, s->border2.p, s->ids2.p);
+  if (F2 > 0)
+    compact_faces<<<blocks_for(F), kThreads, 0, stream>>>(s->flag_f.p, s->scan_f.p, s->scan_v.p, F, F2, s->tri.p, s->tri2.p);
+  if (quad_mode >= 0)
+    compact_quadrics<<<blocks_for(V), kThreads, 0, stream>>>(s->flag_v.p, s->scan_v.p, V, V2, s->quad.p, s->quad2.p);
+  compose_into<<<blocks_for(V_before), kThreads, 0, stream>>>(s->flag_v.p, s->scan_v.p, s->dest.p, V_before, s->into.p);
+  SG_HIP_TRY(hipGetLastError());
+  swap_bufs(s->vs, s->vs2);
+  swap_bufs(s->par, s->par2);
+  swap_bufs(s->border, s->border2);
+  swap_bufs(s->ids, s->ids2);
+  swap_bufs(s->tri, s->tri2);
+  if (quad_mode >= 0) swap_bufs(s->quad, s->quad2);
+  s->V = s->map_after = V2;
+  s->F = F2;
+  return SG_OK;
+}
+
+}  // namespace
+
 int remesh_collapse(sg_remesh* s, float lo2, float thr2, int64_t max_rounds, hipStream_t stream, int64_t* counts,
                     int64_t* n_rounds, int64_t* n_short) {
   *n_rounds = 0;
@@ -990,41 +1323,7 @@ int remesh_collapse(sg_remesh* s, float lo2, float thr2, int64_t max_rounds, hip
     *n_short = (int64_t)c[kShort];
     SG_REQUIRE(W >= 0 && W < V && 2 * W <= F, "sg_remesh_collapse: winner count %lld out of range", (long long)W);
     if (W == 0 || round >= max_rounds) break;
-    const int64_t V2 = V - W, F2 = F - 2 * W;
-    for (auto* b : {&s->flag_v, &s->scan_v})
-      if (int rc = b->reserve(V + 1, false, stream)) return rc;
-    if (int rc = s->dest.reserve(V, false, stream)) return rc;
-    if (int rc = s->vs2.reserve(3 * V2, false, stream)) return rc;
-    if (int rc = s->par2.reserve(2 * V2, false, stream)) return rc;
-    if (int rc = s->border2.reserve(V2, false, stream)) return rc;
-    if (int rc = s->ids2.reserve(V2, false, stream)) return rc;
-    if (int rc = s->tri2.reserve(3 * F2, false, stream)) return rc;
-    const int32_t *flag_v = s->flag_v.p, *flag_f = s->flag_f.p;   // hipCUB's iterator arguments keep their const
-    size_t tb_v = 0;
-    SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_v, flag_v, s->scan_v.p, (int)(V + 1), stream));
-    if (int rc = s->temp.reserve(tb_v ? tb_v : 16, false, stream)) return rc;
-    fill_ones<<<blocks_for(V + 1), kThreads, 0, stream>>>(s->flag_v.p, V);
-    fill_ones<<<blocks_for(F + 1), kThreads, 0, stream>>>(s->flag_f.p, F);
-    collapse_apply<<<blocks_for(n), kThreads, 0, stream>>>(s->win.p, s->vals_b.p, s->twin.p, s->val.p, s->border.p, nc, n, F,
-                                                          s->tri.p, s->flag_f.p, s->flag_v.p, s->dest.p);
-    SG_HIP_TRY(hipGetLastError());
-    size_t tb = s->temp.cap;
-    SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->temp.p, tb, flag_v, s->scan_v.p, (int)(V + 1), stream));
-    tb = s->temp.cap;
-    SG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s->temp.p, tb, flag_f, s->scan_f.p, (int)(F + 1), stream));
-    compact_vertices<<<blocks_for(V), kThreads, 0, stream>>>(s->flag_v.p, s->scan_v.p, s->dest.p, V, V2, s->vs.p, s->par.p,
-                                                            s->border.p, s->ids.p, s->vs2.p, s->par2.p, s->border2.p, s->ids2.p);
-    if (F2 > 0)
-      compact_faces<<<blocks_for(F), kThreads, 0, stream>>>(s->flag_f.p, s->scan_f.p, s->scan_v.p, F, F2, s->tri.p, s->tri2.p);
-    compose_into<<<blocks_for(V_before), kThreads, 0, stream>>>(s->flag_v.p, s->scan_v.p, s->dest.p, V_before, s->into.p);
-    SG_HIP_TRY(hipGetLastError());
-    swap_bufs(s->vs, s->vs2);
-    swap_bufs(s->par, s->par2);
-    swap_bufs(s->border, s->border2);
-    swap_bufs(s->ids, s->ids2);
-    swap_bufs(s->tri, s->tri2);
-    s->V = s->map_after = V2;
-    s->F = F2;
+    if (int rc = apply_and_compact(s, W, V_before, nc, -1, stream)) return rc;
     counts[round] = W;
     *n_rounds = round + 1;
   }
@@ -1044,6 +1343,103 @@ int remesh_collapse_maps(const sg_remesh* s, int64_t* vertex_ids, int64_t* merge
     iota<<<blocks_for(n_before), kThreads, 0, stream>>>(merged_into, n_before);
   }
   SG_HIP_TRY(hipGetLastError());
+  return SG_OK;
+}
+
+namespace {
+// quad = the vertex quadrics of the mesh as it stands: one stable sort of the 3 F corners by vertex, one lane per vertex
+int compute_quadrics(sg_remesh* s, hipStream_t stream) {
+  const int64_t V = s->V, n = 3 * s->F;
+  s->feat_C = -1;                                   // the sorted keys of the analysis are overwritten
+  if (int rc = s->quad.reserve(10 * V, false, stream)) return rc;
+  if (n == 0) {
+    SG_HIP_TRY(hipMemsetAsync(s->quad.p, 0, (size_t)V * 10 * sizeof(double), stream));
+    return SG_OK;
+  }
+  for (auto* b : {&s->keys_a, &s->keys_b})
+    if (int rc = b->reserve(n, false, stream)) return rc;
+  for (auto* b : {&s->vals_a, &s->vals_b})
+    if (int rc = b->reserve(n, false, stream)) return rc;
+  const int bits = bits_for((uint64_t)V, 32);
+  size_t tb = 0;
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, s->keys_a.p, s->keys_b.p, s->vals_a.p, s->vals_b.p, (int)n, 0, bits,
+                                                stream));
+  if (int rc = s->temp.reserve(tb ? tb : 16, false, stream)) return rc;
+  corner_keys<<<blocks_for(n), kThreads, 0, stream>>>(s->tri.p, n, s->keys_a.p, s->vals_a.p);
+  SG_HIP_TRY(hipGetLastError());
+  tb = s->temp.cap;
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(s->temp.p, tb, s->keys_a.p, s->keys_b.p, s->vals_a.p, s->vals_b.p, (int)n, 0, bits,
+                                                stream));
+  vertex_quadrics<<<blocks_for(V), kThreads, 0, stream>>>(s->keys_b.p, s->vals_b.p, n, V, s->tri.p, s->vs.p, s->quad.p);
+  SG_HIP_TRY(hipGetLastError());
+  s->quad_fresh = true;
+  return SG_OK;
+}
+}  // namespace
+
+int remesh_quadrics(sg_remesh* s, double* out, hipStream_t stream) {
+  SG_REQUIRE(s->valid, "sg_remesh_quadrics: the mesh did not pass validation (sg_remesh_query)");
+  if (s->V == 0) return SG_OK;                      // nothing to write, no device to ask
+  SG_REQUIRE(out != nullptr, "sg_remesh_quadrics: null pointer");
+  if (int rc = compute_quadrics(s, stream)) return rc;
+  SG_HIP_TRY(hipMemcpyAsync(out, s->quad.p, (size_t)s->V * 10 * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  return SG_OK;
+}
+
+int remesh_simplify(sg_remesh* s, int64_t target_v, int quadrics_mode, int64_t max_rounds, hipStream_t stream, int64_t* counts,
+                    int64_t* n_rounds, int64_t* n_refused) {
+  SG_REQUIRE(s->valid, "sg_remesh_simplify: the mesh did not pass validation (sg_remesh_query)");
+  SG_REQUIRE(!s->feat, "sg_remesh_simplify: the crease rules are on (sg_remesh_set_feature); crease-aware simplification is "
+                       "not implemented");
+  *n_rounds = 0;
+  *n_refused = 0;
+  s->map_before = s->map_after = s->V;
+  if (s->V == 0) return SG_OK;
+  const int64_t V_before = s->V;
+  if (int rc = s->ids.reserve(V_before, false, stream)) return rc;
+  if (int rc = s->into.reserve(V_before, false, stream)) return rc;
+  iota<<<blocks_for(V_before), kThreads, 0, stream>>>(s->ids.p, V_before);
+  iota<<<blocks_for(V_before), kThreads, 0, stream>>>(s->into.p, V_before);
+  SG_HIP_TRY(hipGetLastError());
+  if (s->F == 0 || s->V <= target_v) return SG_OK;
+  if (!s->quad_fresh)                                          // once, on the mesh the call starts with; a caller that has just
+    if (int rc = compute_quadrics(s, stream)) return rc;       // asked for them (sg_remesh_quadrics) does not pay twice
+  s->quad_fresh = false;
+  for (int64_t round = 0; s->V > target_v && s->F > 0; ++round) {
+    const int64_t V = s->V, F = s->F, n = 3 * F, need = V - target_v;
+    if (int rc = analyse(s, true, stream, true)) return rc;
+    unsigned long long* sorted = reinterpret_cast<unsigned long long*>(s->keys_a.p);   // free once the analysis has sorted
+    const unsigned long long* cand = s->cand.p;
+    size_t tb_keys = 0;
+    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb_keys, cand, sorted, (int)n, 0, 64, stream));
+    if (int rc = s->temp.reserve(tb_keys ? tb_keys : 16, false, stream)) return rc;
+    SG_HIP_TRY(hipMemsetAsync(s->slot.p, 0, (size_t)V * sizeof(uint64_t), stream));
+    simplify_price<<<blocks_for(n), kThreads, 0, stream>>>(s->keys_b.p, s->vals_b.p, s->head.p, s->incl.p, s->twin.p, n, V,
+                                                          s->tri.p, s->vs.p, s->val.p, s->border.p, s->quad.p, s->cand.p,
+                                                          s->ctr.p);
+    SG_HIP_TRY(hipGetLastError());
+    size_t tb = s->temp.cap;
+    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(s->temp.p, tb, cand, sorted, (int)n, 0, 64, stream));
+    simplify_cut<<<1, 1, 0, stream>>>(sorted, n, need, s->ctr.p);
+    simplify_bid<<<blocks_for(n), kThreads, 0, stream>>>(s->cand.p, s->vals_b.p, s->twin.p, s->tri.p, s->val.p, s->border.p,
+                                                        s->ctr.p, n, s->slot.p);
+    simplify_check<<<blocks_for(n), kThreads, 0, stream>>>(s->cand.p, s->vals_b.p, s->twin.p, s->tri.p, s->val.p, s->border.p,
+                                                          s->slot.p, n, s->win.p, s->ctr.p);
+    SG_HIP_TRY(hipGetLastError());
+    unsigned long long c[kCounters];
+    if (int rc = read_counters(s, c, stream)) return rc;       // the round's one synchronisation: count -> apply
+    const int64_t C = (int64_t)c[kCand], A = (int64_t)c[kAdmitted], W = (int64_t)c[kWinners];
+    *n_refused = (int64_t)c[kRefused];
+    SG_REQUIRE(C >= 0 && C <= n && A >= 0 && A <= need && A <= C && W >= 0 && W <= A && W < V && 2 * W <= F,
+               "sg_remesh_simplify: counts out of range (%lld candidates, %lld admitted, %lld winners)", (long long)C,
+               (long long)A, (long long)W);
+    if (W == 0 || round >= max_rounds) break;
+    if (int rc = apply_and_compact(s, W, V_before, nullptr, quadrics_mode, stream)) return rc;
+    counts[3 * round] = C;
+    counts[3 * round + 1] = A;
+    counts[3 * round + 2] = W;
+    *n_rounds = round + 1;
+  }
   return SG_OK;
 }
 

@@ -406,6 +406,9 @@ int remesh_flip(sg_remesh* s, int64_t max_rounds, hipStream_t stream, int64_t* c
 int remesh_collapse(sg_remesh* s, float lo2, float thr2, int64_t max_rounds, hipStream_t stream, int64_t* counts,
                     int64_t* n_rounds, int64_t* n_short);
 int remesh_collapse_maps(const sg_remesh* s, int64_t* vertex_ids, int64_t* merged_into, hipStream_t stream);
+int remesh_simplify(sg_remesh* s, int64_t target_v, int quadrics_mode, int64_t max_rounds, hipStream_t stream, int64_t* counts,
+                    int64_t* n_rounds, int64_t* n_refused);
+int remesh_quadrics(sg_remesh* s, double* out, hipStream_t stream);
 int remesh_export(const sg_remesh* s, float* vs, int64_t* faces, int64_t* parents, uint8_t* border, hipStream_t stream);
 void remesh_set_feature(sg_remesh* s, bool enabled, double cos_t);
 int remesh_features(sg_remesh* s, hipStream_t stream, uint8_t* vclass, int64_t* crease_nbr, int64_t* n_crease);

@@ -300,9 +300,24 @@ class DeviceMesh:
     (clusters of 1 .. 5), positions (midpoints of the collapses, as util/mesh.py:564), the surviving triangles, and the
     quotient graph as ``edge_index``.  The collapse ORDER differs from a sequential heap, so the clusters are not the
     reference's clusters; tests/test_gpu_parity.py compares the two hierarchies by what they are for: geometric error of
-    the coarse meshes, and the loss an MGCN trained on either reaches."""
+    the coarse meshes, and the loss an MGCN trained on either reaches.
 
-    def __init__(self, vs, faces, device="cuda", path: str = "./mesh.obj", pool_hash=None, edge_index=None):
+    ``criterion`` (``"qem"``, ``"length"`` or ``"collapse"``) is remembered, is the default of ``simplification`` and is carried
+    to the coarse level, so ``MGCN.__init__``, which calls ``simplification(target_v)`` bare, builds its whole hierarchy with
+    it.  ``"collapse"`` is ``simplify.simplify_mesh``: guarded quadric edge collapses on the device, specified in
+    semigcn_amd/simplify.py, with the same artefacts, run with ``quadrics="sum"``: a kept vertex that carries only its own
+    quadric prices a second merge into it too low, and on the regular torus the hierarchy then has more summed cluster
+    quadric error than ``"qem"`` ("Simplification", has the figures of both).  Its clusters have no size cap.  On a closed mesh the kept vertex is
+    the cluster's smallest member, so coarse ids ascend with the smallest member as above; on an open mesh a border vertex is
+    kept whatever its id, and coarse ids ascend with the SURVIVING vertex."""
+
+    CRITERIA = ("qem", "length", "collapse")
+
+    def __init__(self, vs, faces, device="cuda", path: str = "./mesh.obj", pool_hash=None, edge_index=None,
+                 criterion: str = "qem"):
+        if criterion not in self.CRITERIA:
+            raise ValueError(f"criterion must be one of {self.CRITERIA}, got {criterion!r}")
+        self.criterion = criterion
         device = torch.device(device)
         self.vs = torch.as_tensor(vs).to(device=device, dtype=torch.float32)
         self.topology = MeshTopology(faces, self.vs.shape[0], device, with_f2f=False)
@@ -311,7 +326,10 @@ class DeviceMesh:
         self.pool_hash = pool_hash
         self.path = path
 
-    def simplification(self, target_v: int, criterion: str = "qem") -> "DeviceMesh":
+    def simplification(self, target_v: int, criterion: Optional[str] = None) -> "DeviceMesh":
+        criterion = self.criterion if criterion is None else criterion
+        if criterion not in self.CRITERIA:
+            raise ValueError("criterion must be 'qem', 'length' or 'collapse'")
         V = self.vs.shape[0]
         half = self.edge_index.shape[1] // 2
         und = self.edge_index[:, :half].t().contiguous()
@@ -323,7 +341,9 @@ class DeviceMesh:
             coarse_of, Vc = contract_matching(und, (d * d).sum(1), V, target_v)
             cvs = capi.PoolHandle(fine, coarse_of, V, Vc).pool_mean(self.vs.contiguous())
         else:
-            raise ValueError("criterion must be 'qem' or 'length'")
+            from .simplify import simplify_mesh
+            out = simplify_mesh(self.vs, self.faces, target_v=int(target_v), quadrics="sum", error_report=False)
+            coarse_of, Vc, cvs = out.coarse_of, int(out.vs.shape[0]), out.vs
         cf = coarse_of[self.faces]
         alive = (cf[:, 0] != cf[:, 1]) & (cf[:, 1] != cf[:, 2]) & (cf[:, 2] != cf[:, 0])
         ce = coarse_of[und]
@@ -332,5 +352,5 @@ class DeviceMesh:
         e = torch.stack([key // Vc, key % Vc])
         out = DeviceMesh(cvs, cf[alive], self.vs.device, self.path,
                          pool_hash=torch.stack([fine, coarse_of], 1).cpu().numpy(),
-                         edge_index=torch.cat([e, e.flip(0)], dim=1).contiguous())
+                         edge_index=torch.cat([e, e.flip(0)], dim=1).contiguous(), criterion=self.criterion)
         return out
