@@ -468,6 +468,58 @@ SG_API int sg_fill_plan(sg_fill* s, int64_t max_hole_edges, void* stream, int64_
 SG_API int sg_fill_emit(sg_fill* s, const float* vs, float* new_vs, int64_t* new_faces, uint8_t* filled_out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Thin-plate fairing of the free vertices of a mesh -- what MeshFix does to its
+ * patches after it has meshed them: a Jacobi-preconditioned conjugate-gradient
+ * solve in float64.  The rule (graph, rows, energy, system, stop test) is
+ * specified in semigcn_amd/holes.py, "Thin-plate fairing".
+ *
+ * sg_fair_create: from faces int64 [F,3] over V vertices and free uint8 [V]
+ *   (device; non-zero = the vertex is an unknown) builds the distinct-neighbour
+ *   lists of the rows S = free u N(free), the compact index lists of the free
+ *   vertices and of S (both ascending), 1/d and diag(A), and checks with a
+ *   union-find over the free-free edges that every class of free vertices has an
+ *   edge to a fixed vertex (A is SPD exactly then).  A face index outside [0, V)
+ *   or a face with a repeated vertex gives SG_ERR_INVALID.  A free vertex without
+ *   edges or a class without a fixed neighbour makes the system singular: the
+ *   plan is still returned, sg_fair_query names the vertex, and sg_fair_diagonal
+ *   / sg_fair_apply / sg_fair_solve fail.  Synchronises the stream.
+ * sg_fair_query: info[8] (host) = number of free vertices nf, number of rows
+ *   |S|, entries of the rows' neighbour lists, the smallest offending vertex
+ *   (-1: none), why (0: nothing; 1: the smallest free vertex without edges; 2:
+ *   the smallest vertex of a free class without an edge to a fixed vertex),
+ *   number of block partials per dot product, launches per iteration, 0.
+ * sg_fair_diagonal: copies diag(A)_i = 1 + sum_{j in N(i)} (1/d_j)^2, float64
+ *   [nf] in free-list order, summed in ascending neighbour order, to a device
+ *   array of the caller.  Asynchronous.
+ * sg_fair_apply: q = A p for p float64 [nf] over the free list (device; q != p),
+ *   by the two gathers of the solve: y_i = p_i - (1/d_i) sum p_j over the rows S,
+ *   q_i = y_i - sum y_j (1/d_j) over the free rows, in ascending neighbour order
+ *   with plain multiplies and adds: bit-reproducible, and equal to numpy bit for
+ *   bit.  Asynchronous; uses the plan's buffers: one call at a time per plan.
+ * sg_fair_solve: from in float32 [V,3] to out float32 [V,3] (may be the same
+ *   array).  x0 = the input positions; every coordinate has its own alpha, beta
+ *   and stop test ||r||^2 <= tol^2 ||b||^2 on the recursive residual, and is
+ *   frozen (alpha = beta = 0) once it has met it; the solve ends when all three
+ *   are frozen or after max_iter iterations.  The scalars stay on the device;
+ *   the host reads one word every check_every iterations, which does not change
+ *   the result.  Four launches per iteration; dot products are fixed block
+ *   partials added up in a fixed order: no floating-point atomics, two runs give
+ *   identical bytes.  The free vertices are rounded to float32 once, every other
+ *   vertex is copied bit for bit.  Returns (host) the iterations taken, the
+ *   relative residual ||r|| / ||b|| per coordinate [3] and whether every
+ *   coordinate met its test; reaching max_iter is not an error.  Synchronises
+ *   the stream.  tol < 0, max_iter < 0 or check_every < 1 gives SG_ERR_INVALID.
+ * ------------------------------------------------------------------------- */
+typedef struct sg_fair sg_fair;
+SG_API int sg_fair_create(const int64_t* faces, int64_t F, int64_t V, const uint8_t* free, void* stream, sg_fair** out);
+SG_API int sg_fair_destroy(sg_fair* s);
+SG_API int sg_fair_query(const sg_fair* s, int64_t* info);
+SG_API int sg_fair_diagonal(const sg_fair* s, double* out, void* stream);
+SG_API int sg_fair_apply(sg_fair* s, const double* p, double* q, void* stream);
+SG_API int sg_fair_solve(sg_fair* s, const float* in, float* out, double tol, int64_t max_iter, int64_t check_every,
+                         void* stream, int64_t* iterations, double* relative_residual, int* converged);
+
+/* ------------------------------------------------------------------------- *
  * Connected components -- replaces the first step of MeshFix.repair()
  * (preprocess/prepare.py:28-33): label the components of a triangle list, keep
  * some of them, compact vertices and faces.  The definitions (connectivities,

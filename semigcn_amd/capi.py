@@ -212,6 +212,13 @@ _SIGNATURES = {
     "sg_fill_loops": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_fill_plan": (c_int, [c_void_p, c_int64, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
     "sg_fill_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_fair_create": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "sg_fair_destroy": (c_int, [c_void_p]),
+    "sg_fair_query": (c_int, [c_void_p, POINTER(c_int64)]),
+    "sg_fair_diagonal": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "sg_fair_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_fair_solve": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_double, c_int64, c_int64, c_void_p, POINTER(c_int64),
+                              POINTER(ctypes.c_double), POINTER(c_int)]),
     "sg_parts_create": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, POINTER(c_void_p)]),
     "sg_parts_destroy": (c_int, [c_void_p]),
     "sg_parts_query": (c_int, [c_void_p, POINTER(c_int64)]),
@@ -1585,6 +1592,70 @@ class FillPlan(_OwnedHandle):
             _check(load().sg_fill_emit(self._h, _ptr(vs), _ptr(new_vs), _ptr(new_faces), _ptr(filled), _stream(vs)),
                    "sg_fill_emit")
         return filled[: self.num_loops]
+
+
+class FairPlan(_OwnedHandle):
+    """Owns one sg_fair (csrc/mesh_fair.hip): the thin-plate system of the vertices ``free`` bool [V] of a triangle list
+    (the rule is specified in semigcn_amd/holes.py, "Thin-plate fairing") and the vectors of its conjugate-gradient solve.
+    ``bad_vertex`` / ``bad_kind`` say why a system is singular; ``diagonal`` / ``apply`` / ``solve`` then raise.  One call
+    at a time per plan."""
+
+    _destroy = "sg_fair_destroy"
+    _query_fn, _query_len = "sg_fair_query", 8
+
+    def __init__(self, faces: torch.Tensor, num_vertices: int, free: torch.Tensor):
+        _require_device(faces, "faces")
+        _require_device(free, "free")
+        faces = _faces_arg(faces)
+        if free.numel() != int(num_vertices) or free.device != faces.device:
+            raise SemigcnLibraryError(f"free must hold {int(num_vertices)} entries on {faces.device}, got "
+                                      f"{tuple(free.shape)} on {free.device}")
+        free = (free.reshape(-1) != 0).contiguous()                      # bool: one byte per vertex, 0 / 1
+        self.device, self.num_vertices, self.num_faces = faces.device, int(num_vertices), faces.shape[0]
+        self._create("sg_fair_create", faces.device, _ptr(faces), faces.shape[0], self.num_vertices, _ptr(free), _stream(faces))
+        info = self._query()
+        self.num_free, self.num_rows, self.nnz, self.bad_vertex, self.bad_kind = (int(v) for v in info[:5])
+        self.num_partials, self.launches_per_iteration = int(info[5]), int(info[6])
+
+    @property
+    def solvable(self) -> bool:
+        return self.bad_kind == 0
+
+    def diagonal(self) -> torch.Tensor:
+        """diag(A), float64 [nf] in free-list order."""
+        self._open()
+        out = torch.empty(self.num_free, dtype=torch.float64, device=self.device)
+        with _on_device(self.device):
+            _check(load().sg_fair_diagonal(self._h, _ptr(out), _stream(out)), "sg_fair_diagonal")
+        return out
+
+    def apply(self, p: torch.Tensor) -> torch.Tensor:
+        """q = A p for p float64 [nf] over the free list (ascending vertex id)."""
+        _require_device(p, "p")
+        if p.dtype != torch.float64 or tuple(p.shape) != (self.num_free,) or p.device != self.device:
+            raise SemigcnLibraryError(f"p must be float64 [{self.num_free}] on {self.device}, got {p.dtype} {tuple(p.shape)} "
+                                      f"on {p.device}")
+        self._open()
+        p = p.detach().contiguous()
+        q = torch.empty_like(p)
+        with _on_device(self.device):
+            _check(load().sg_fair_apply(self._h, _ptr(p), _ptr(q), _stream(p)), "sg_fair_apply")
+        return q
+
+    def solve(self, vs: torch.Tensor, tol: float = 1e-10, max_iter: int = 10000, check_every: int = 32):
+        """(float32 [V, 3], info): the free vertices at the minimiser, every other vertex bit for bit; ``info`` holds
+        ``iterations``, ``relative_residual`` (per coordinate), ``converged`` and ``n_free``."""
+        _require_device(vs, "vs")
+        _vs_arg(vs, self)
+        self._open()
+        vs = vs.detach().contiguous()
+        out = torch.empty_like(vs)
+        it, ok, res = c_int64(), c_int(), (ctypes.c_double * 3)()
+        with _on_device(self.device):
+            _check(load().sg_fair_solve(self._h, _ptr(vs), _ptr(out), float(tol), int(max_iter), int(check_every), _stream(vs),
+                                        byref(it), res, byref(ok)), "sg_fair_solve")
+        return out, {"iterations": int(it.value), "relative_residual": [float(v) for v in res], "converged": bool(ok.value),
+                     "n_free": self.num_free}
 
 
 class PartsPlan(_OwnedHandle):

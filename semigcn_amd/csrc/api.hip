@@ -599,6 +599,49 @@ SG_API int sg_fill_emit(sg_fill* s, const float* vs, float* new_vs, int64_t* new
   return fill_emit(s, vs, new_vs, new_faces, filled_out, (hipStream_t)stream);
 }
 
+// thin-plate fairing of the patches (semigcn_amd/holes.py, "Thin-plate fairing"): csrc/mesh_fair.hip
+SG_API int sg_fair_create(const int64_t* faces, int64_t F, int64_t V, const uint8_t* free, void* stream, sg_fair** out) {
+  SG_REQUIRE(out != nullptr, "sg_fair_create: null out");
+  *out = nullptr;
+  SG_REQUIRE(F >= 0 && V >= 0, "sg_fair_create: negative size (F = %lld, V = %lld)", (long long)F, (long long)V);
+  SG_REQUIRE((F == 0 || faces) && (V == 0 || free), "sg_fair_create: null pointer");
+  return fair_create(faces, F, V, free, (hipStream_t)stream, out);
+}
+
+SG_API int sg_fair_destroy(sg_fair* s) {
+  destroy_fair(s);
+  return SG_OK;
+}
+
+SG_API int sg_fair_query(const sg_fair* s, int64_t* info) {
+  SG_REQUIRE(s != nullptr, "sg_fair_query: null plan");
+  SG_REQUIRE(info != nullptr, "sg_fair_query: null pointer");
+  fair_query(s, info);
+  return SG_OK;
+}
+
+SG_API int sg_fair_diagonal(const sg_fair* s, double* out, void* stream) {
+  SG_REQUIRE(s != nullptr, "sg_fair_diagonal: null plan");
+  SG_REQUIRE(out != nullptr, "sg_fair_diagonal: null pointer");
+  return fair_diagonal(s, out, (hipStream_t)stream);
+}
+
+SG_API int sg_fair_apply(sg_fair* s, const double* p, double* q, void* stream) {
+  SG_REQUIRE(s != nullptr, "sg_fair_apply: null plan");
+  SG_REQUIRE(p && q && p != q, "sg_fair_apply: null pointer, or q is p");
+  return fair_apply(s, p, q, (hipStream_t)stream);
+}
+
+SG_API int sg_fair_solve(sg_fair* s, const float* in, float* out, double tol, int64_t max_iter, int64_t check_every,
+                         void* stream, int64_t* iterations, double* relative_residual, int* converged) {
+  SG_REQUIRE(s != nullptr, "sg_fair_solve: null plan");
+  SG_REQUIRE(in && out && iterations && relative_residual && converged, "sg_fair_solve: null pointer");
+  SG_REQUIRE(tol >= 0.0, "sg_fair_solve: tol must be >= 0, got %g", tol);
+  SG_REQUIRE(max_iter >= 0 && check_every >= 1, "sg_fair_solve: max_iter must be >= 0 and check_every >= 1, got %lld and %lld",
+             (long long)max_iter, (long long)check_every);
+  return fair_solve(s, in, out, tol, max_iter, check_every, (hipStream_t)stream, iterations, relative_residual, converged);
+}
+
 // the component selection of MeshFix.repair() (preprocess/prepare.py:28-33): csrc/mesh_parts.hip
 SG_API int sg_parts_create(const int64_t* faces, int64_t F, int64_t V, int connectivity, void* stream, sg_parts** out) {
   SG_REQUIRE(out != nullptr, "sg_parts_create: null out");

@@ -1,8 +1,8 @@
-// What the mesh stages (mesh_prep, mesh_smooth, mesh_fill, mesh_parts, mesh_manifold, mesh_remesh, mesh_dist, mesh_isect) share on the host
+// What the mesh stages (mesh_prep, mesh_smooth, mesh_fill, mesh_parts, mesh_manifold, mesh_remesh, mesh_dist, mesh_isect, mesh_fair) share on the host
 // side: typed device buffers that own their memory, the launch geometry, the bit count behind the radix-sort ranges, the
-// exclusive scan, and the one kernel and one device helper that were literal copies.  The rule that goes with it: device
+// exclusive scan, and the kernels and the one device helper that were literal copies.  The rule that goes with it: device
 // memory of a plan or of a call is a typed member or local that frees itself -- never a raw pointer on a hand-kept free list.
-// No floating-point code belongs here: mesh_isect.hip, mesh_remesh.hip and mesh_manifold.hip are built with
+// No floating-point code belongs here: mesh_isect.hip, mesh_remesh.hip, mesh_manifold.hip and mesh_fair.hip are built with
 // -ffp-contract=off, the others not.
 #pragma once
 #include <hipcub/hipcub.hpp>
@@ -100,6 +100,44 @@ template <class T>
 __global__ void widen32(const int32_t* __restrict__ in, int64_t n, T* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = in[i];
+}
+
+// The neighbour lists of mesh_smooth.hip and mesh_fair.hip start here (templates for the same reason).  Face-edge
+// h = 3 f + i joins a = faces[f][i] and b = faces[f][(i+1)%3]; it puts b on a's list and a on b's: keys (a << 32 | b) and
+// (b << 32 | a).  flags[0]: vertex id out of range; flags[1]: degenerate face (repeated vertex).
+template <class Key>
+__global__ void directed_keys(const int64_t* __restrict__ faces, int64_t n_half, int64_t V, Key* __restrict__ keys,
+                              int* __restrict__ flags) {
+  const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (h >= n_half) return;
+  const int64_t f = h / 3;
+  const int i = (int)(h - 3 * f);
+  const int64_t a = faces[3 * f + i], b = faces[3 * f + next3(i)];
+  Key k0 = ~(Key)0, k1 = ~(Key)0;
+  if (a < 0 || a >= V || b < 0 || b >= V) {
+    flags[0] = 1;
+  } else {
+    if (a == b) flags[1] = 1;
+    k0 = ((Key)a << 32) | (Key)b;
+    k1 = ((Key)b << 32) | (Key)a;
+  }
+  keys[2 * h] = k0;
+  keys[2 * h + 1] = k1;
+}
+
+// rowptr[v] = first run whose source vertex is >= v (the runs are sorted by (source, neighbour))
+template <class Key>
+__global__ void row_starts(const Key* __restrict__ ukeys, int64_t n, int64_t V, int32_t* __restrict__ rowptr) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v > V) return;
+  const Key key = (Key)v << 32;
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (ukeys[mid] < key) lo = mid + 1;
+    else hi = mid;
+  }
+  rowptr[v] = (int32_t)lo;
 }
 
 }  // namespace

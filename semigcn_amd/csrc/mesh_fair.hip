@@ -1,0 +1,695 @@
+// Thin-plate fairing of the free vertices of a mesh: a Jacobi-preconditioned conjugate-gradient solve in float64, on the device.
+// The rule is specified in semigcn_amd/holes.py ("Thin-plate fairing"); tests/fair_oracle.py restates it in numpy.
+//
+//   (Lx)_i = x_i - (1/d_i) sum_{j in N(i)} x_j over the distinct neighbours; rows S = free u N(free); M = the rows S of L;
+//   A = M_free^T M_free, b = -M_free^T M_fixed x_fixed, three right-hand sides (x, y, z).
+//
+// Index spaces.  The plan numbers the vertices of S (ascending vertex id) and, among them, the free ones (ascending too), and
+// keeps the neighbour lists of the rows S only, each column three times: the vertex id (col_g, for the positions the fixed
+// vertices are read from), the free index (col_f, -1 = fixed) and the S index (col_s, -1 = outside S).  Ascending vertex id is
+// ascending index in both numberings, so every sum below runs in ascending neighbour order.
+//
+// A p is two gathers, one lane per row (the rows are short: valence near 6):
+//   fair_rows   y_i = p_i - (1/d_i) sum_{j free} p_j   for i in S (p_i = 0 when i is fixed); also yw_i = y_i (1/d_i)
+//   fair_cols   q_i = y_i - sum_{j in N(i)} yw_j        for i free (every neighbour of a free vertex is in S)
+// An iteration is FOUR launches: fair_rows, fair_cols (with the p.q partials), fair_update (finishes p.q, x += a p, r -= a q,
+// z = r / diag, the r.z and r.r partials) and fair_direction (finishes r.z and r.r, freezes, p = z + b p, writes the state).
+// The scalars live in two FairState records the iterations ping-pong between; the host reads one word of the current one
+// every check_every iterations.
+//
+// Dot products: block b sums the `chunk` consecutive indices from b * chunk (each thread its own in ascending order, then a
+// fixed tree over the block), and EVERY block of the next launch adds the nb <= 1024 partials up the same way -- the same
+// total in every block, without a launch of its own.  No floating-point atomics: two runs give identical bytes.
+// Built with -ffp-contract=off: the products and sums of fair_rows / fair_cols / fair_diag round one by one, as numpy's do.
+#include <cmath>
+#include <memory>
+#include <new>
+
+#include "mesh_common.h"
+#include "mesh_union.h"
+
+namespace sg {
+namespace {
+
+constexpr int kMaxPartials = 1024;
+constexpr int kNoVertex = 0x7f7f7f7f;      // what a memset of 0x7f leaves: above every vertex id the plan takes
+
+struct FairState {
+  double rz[3], rr[3], bb[3], thr[3];   // r.z, r.r, b.b, tol^2 b.b per coordinate
+  int32_t frozen[3];
+  int32_t all_frozen;                   // the word the host polls
+  int64_t done_iter;                    // the iteration after which every coordinate was frozen; -1 until then
+};
+
+}  // namespace
+}  // namespace sg
+
+struct sg_fair {
+  int64_t V = 0, nf = 0, nS = 0, nnz = 0;
+  int64_t bad_vertex = -1;
+  int bad_kind = 0;                       // 1: a free vertex without edges; 2: a free class without an edge to a fixed vertex
+  int nb = 1;                             // blocks (= partials) of the kernels over the free list
+  int64_t chunk = sg::kThreads;           // indices per block
+  sg::DeviceBuf<int32_t> rowptr;          // [nS + 1]
+  sg::DeviceBuf<int32_t> col_g, col_f, col_s;   // [nnz]
+  sg::DeviceBuf<int32_t> s_glob, s_free;  // [nS] vertex id, free index or -1
+  sg::DeviceBuf<int32_t> free_s;          // [nf] S index
+  sg::DeviceBuf<double> invd;             // [nS] 1 / d
+  sg::DeviceBuf<double> diag;             // [nf] 1 + sum_j (1/d_j)^2
+  sg::DeviceBuf<double> x, r, z, p, q;    // [nf, 3]
+  sg::DeviceBuf<double> y, yw;            // [nS, 3]
+  sg::DeviceBuf<double> part_a, part_b;   // [nb, 3] p.q (b.b while the solve is set up); [nb, 6] r.z, r.r
+  sg::DeviceBuf<sg::FairState> state;     // [2]
+};
+
+namespace sg {
+namespace {
+
+// ---- plan ------------------------------------------------------------------------------------------------------------
+// in_s[i]: i is free or has a free neighbour; rowlen[i]: its valence when it is, else 0.  bad[0] = smallest free vertex
+// without edges.  The three arrays have V + 1 entries (the last one 0) so that their exclusive sums end in the totals.
+__global__ void fair_mark(const uint8_t* __restrict__ free, const int32_t* __restrict__ rowptr, const uint64_t* __restrict__ ukeys,
+                          int64_t V, int32_t* __restrict__ is_free, int32_t* __restrict__ in_s, int32_t* __restrict__ rowlen,
+                          int* __restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > V) return;
+  int fr = 0, s = 0, len = 0;
+  if (i < V) {
+    const int b = rowptr[i], e = rowptr[i + 1];
+    fr = free[i] != 0;
+    if (fr && b == e) atomicMin(bad, (int)i);
+    s = fr;
+    for (int j = b; j < e && !s; ++j) s = free[ukeys[j] & 0xffffffffull] != 0;
+    len = s ? e - b : 0;
+  }
+  is_free[i] = fr;
+  in_s[i] = s;
+  rowlen[i] = len;
+}
+
+// the rows S in their compact numbering (f_idx, s_idx, out_ptr: the exclusive sums of fair_mark's arrays)
+__global__ void fair_fill(const int32_t* __restrict__ rowptr, const uint64_t* __restrict__ ukeys, const uint8_t* __restrict__ free,
+                          const int32_t* __restrict__ in_s, const int32_t* __restrict__ f_idx, const int32_t* __restrict__ s_idx,
+                          const int32_t* __restrict__ out_ptr, int64_t V, int32_t* __restrict__ c_rowptr,
+                          int32_t* __restrict__ col_g, int32_t* __restrict__ col_f, int32_t* __restrict__ col_s,
+                          int32_t* __restrict__ s_glob, int32_t* __restrict__ s_free, int32_t* __restrict__ free_s,
+                          double* __restrict__ invd) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > V) return;
+  if (i == V) {
+    c_rowptr[s_idx[V]] = out_ptr[V];
+    return;
+  }
+  if (!in_s[i]) return;
+  const int s = s_idx[i], b = rowptr[i], e = rowptr[i + 1];
+  int o = out_ptr[i];
+  c_rowptr[s] = o;
+  s_glob[s] = (int32_t)i;
+  const bool fr = free[i] != 0;
+  s_free[s] = fr ? f_idx[i] : -1;
+  if (fr) free_s[f_idx[i]] = s;
+  invd[s] = 1.0 / (double)(e - b);          // e > b: a vertex of S has a neighbour
+  for (int j = b; j < e; ++j, ++o) {
+    const int32_t g = (int32_t)(ukeys[j] & 0xffffffffull);
+    col_g[o] = g;
+    col_f[o] = free[g] ? f_idx[g] : -1;
+    col_s[o] = in_s[g] ? s_idx[g] : -1;
+  }
+}
+
+__global__ void fair_diag(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col_s, const int32_t* __restrict__ free_s,
+                          const double* __restrict__ invd, int64_t nf, double* __restrict__ diag) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  const int s = free_s[f], e1 = rowptr[s + 1];
+  double acc = 1.0;
+  for (int e = rowptr[s]; e < e1; ++e) {
+    const int j = col_s[e];
+    if (j >= 0) {
+      const double w = invd[j];
+      acc += w * w;
+    }
+  }
+  diag[f] = acc;
+}
+
+// the classes of the free vertices under free-free edges (mesh_union.h); every edge once, from its larger end
+__global__ void fair_unite(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col_f, const int32_t* __restrict__ free_s,
+                           int64_t nf, int32_t* __restrict__ parent) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  const int s = free_s[f], e1 = rowptr[s + 1];
+  for (int e = rowptr[s]; e < e1; ++e) {
+    const int g = col_f[e];
+    if (g >= 0 && g < f) unite(parent, (int32_t)f, g);
+  }
+}
+
+// after flatten: a class with an edge to a fixed vertex is anchored (every writer stores the same 1)
+__global__ void fair_anchor(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col_f, const int32_t* __restrict__ free_s,
+                            const int32_t* __restrict__ parent, int64_t nf, int32_t* __restrict__ anchored) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  const int s = free_s[f], e1 = rowptr[s + 1];
+  for (int e = rowptr[s]; e < e1; ++e) {
+    if (col_f[e] < 0) {
+      anchored[parent[f]] = 1;
+      return;
+    }
+  }
+}
+
+// bad[1] = smallest vertex of a class that is not anchored (a root is the smallest member of its class)
+__global__ void fair_floating(const int32_t* __restrict__ parent, const int32_t* __restrict__ anchored,
+                              const int32_t* __restrict__ free_s, const int32_t* __restrict__ s_glob, int64_t nf,
+                              int* __restrict__ bad) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  if (parent[f] == (int32_t)f && !anchored[f]) atomicMin(bad + 1, (int)s_glob[free_s[f]]);
+}
+
+// ---- sums ------------------------------------------------------------------------------------------------------------
+// every thread leaves with the block's sums: lanes by shuffle, the four waves in a fixed order
+template <int N>
+__device__ inline void block_sum(double (&v)[N], double (*s_w)[kThreads / 64]) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
+  }
+  __syncthreads();                      // whoever still reads s_w from a call before is done
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) s_w[k][threadIdx.x >> 6] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = (s_w[k][0] + s_w[k][1]) + (s_w[k][2] + s_w[k][3]);
+}
+
+// the totals of nb block partials of N values each, in every thread of every block that asks
+template <int N>
+__device__ inline void total_of(const double* __restrict__ part, int nb, double (&t)[N], double (*s_w)[kThreads / 64]) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) t[k] = 0.0;
+  for (int b = threadIdx.x; b < nb; b += kThreads) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) t[k] += part[(int64_t)b * N + k];
+  }
+  block_sum<N>(t, s_w);
+}
+
+// ---- A p -------------------------------------------------------------------------------------------------------------
+template <int NC>
+__global__ __launch_bounds__(kThreads) void fair_rows(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col_f,
+                                                      const int32_t* __restrict__ s_free, const double* __restrict__ invd,
+                                                      const double* __restrict__ p, int64_t nS, double* __restrict__ y,
+                                                      double* __restrict__ yw) {
+  const int64_t s = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (s >= nS) return;
+  double acc[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) acc[c] = 0.0;
+  const int e1 = rowptr[s + 1];
+  for (int e = rowptr[s]; e < e1; ++e) {
+    const int f = col_f[e];
+    if (f >= 0) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) acc[c] += p[(int64_t)NC * f + c];
+    }
+  }
+  const int fi = s_free[s];
+  const double w = invd[s];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const double own = fi >= 0 ? p[(int64_t)NC * fi + c] : 0.0;
+    const double v = own - w * acc[c];
+    y[NC * s + c] = v;
+    yw[NC * s + c] = v * w;
+  }
+}
+
+// the same rows from the float32 positions of ALL vertices (ZERO_FREE: with the free ones taken as 0, which gives -b)
+template <bool ZERO_FREE>
+__global__ __launch_bounds__(kThreads) void fair_rows_vs(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col_g,
+                                                         const int32_t* __restrict__ col_f, const int32_t* __restrict__ s_glob,
+                                                         const int32_t* __restrict__ s_free, const double* __restrict__ invd,
+                                                         const float* __restrict__ vs, int64_t nS, double* __restrict__ y,
+                                                         double* __restrict__ yw) {
+  const int64_t s = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (s >= nS) return;
+  double acc[3] = {0.0, 0.0, 0.0};
+  const int e1 = rowptr[s + 1];
+  for (int e = rowptr[s]; e < e1; ++e) {
+    if (ZERO_FREE && col_f[e] >= 0) continue;
+    const int64_t g = col_g[e];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] += (double)vs[3 * g + c];
+  }
+  const bool zero_own = ZERO_FREE && s_free[s] >= 0;
+  const int64_t g = s_glob[s];
+  const double w = invd[s];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double own = zero_own ? 0.0 : (double)vs[3 * g + c];
+    const double v = own - w * acc[c];
+    y[3 * s + c] = v;
+    yw[3 * s + c] = v * w;
+  }
+}
+
+// q = M^T y over the free list; DOT: also this block's partial of p.q
+template <int NC, bool DOT>
+__global__ __launch_bounds__(kThreads) void fair_cols(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col_s,
+                                                      const int32_t* __restrict__ free_s, const double* __restrict__ y,
+                                                      const double* __restrict__ yw, const double* __restrict__ p, int64_t nf,
+                                                      int64_t chunk, double* __restrict__ q, double* __restrict__ part) {
+  __shared__ double s_w[NC][kThreads / 64];
+  double dot[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) dot[c] = 0.0;
+  const int64_t base = (int64_t)blockIdx.x * chunk;
+  for (int64_t t = threadIdx.x; t < chunk; t += kThreads) {
+    const int64_t f = base + t;
+    if (f >= nf) break;
+    const int s = free_s[f], e1 = rowptr[s + 1];
+    double acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c] = 0.0;
+    for (int e = rowptr[s]; e < e1; ++e) {
+      const int j = col_s[e];
+      if (j >= 0) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) acc[c] += yw[(int64_t)NC * j + c];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const double v = y[(int64_t)NC * s + c] - acc[c];
+      q[NC * f + c] = v;
+      if (DOT) dot[c] += p[NC * f + c] * v;
+    }
+  }
+  if (DOT) {
+    block_sum<NC>(dot, s_w);
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) part[(int64_t)blockIdx.x * NC + c] = dot[c];
+    }
+  }
+}
+
+// ---- the solve -------------------------------------------------------------------------------------------------------
+// q holds M^T M x_fixed = -b: this block's partial of b.b
+__global__ __launch_bounds__(kThreads) void fair_init_b(const double* __restrict__ q, int64_t nf, int64_t chunk,
+                                                        double* __restrict__ part) {
+  __shared__ double s_w[3][kThreads / 64];
+  double bb[3] = {0.0, 0.0, 0.0};
+  const int64_t base = (int64_t)blockIdx.x * chunk;
+  for (int64_t t = threadIdx.x; t < chunk; t += kThreads) {
+    const int64_t f = base + t;
+    if (f >= nf) break;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) bb[c] += q[3 * f + c] * q[3 * f + c];
+  }
+  block_sum<3>(bb, s_w);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) part[(int64_t)blockIdx.x * 3 + c] = bb[c];
+  }
+}
+
+// q holds M^T M x_all = -(b - A x0): x = x0, r = -q, z = r / diag, p = z, and the partials of r.z and r.r
+__global__ __launch_bounds__(kThreads) void fair_init_r(const double* __restrict__ q, const double* __restrict__ diag,
+                                                        const float* __restrict__ vs, const int32_t* __restrict__ free_s,
+                                                        const int32_t* __restrict__ s_glob, int64_t nf, int64_t chunk,
+                                                        double* __restrict__ x, double* __restrict__ r, double* __restrict__ z,
+                                                        double* __restrict__ p, double* __restrict__ part) {
+  __shared__ double s_w[6][kThreads / 64];
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const int64_t base = (int64_t)blockIdx.x * chunk;
+  for (int64_t t = threadIdx.x; t < chunk; t += kThreads) {
+    const int64_t f = base + t;
+    if (f >= nf) break;
+    const int64_t g = s_glob[free_s[f]];
+    const double d = diag[f];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double rv = -q[3 * f + c], zv = rv / d;
+      x[3 * f + c] = (double)vs[3 * g + c];
+      r[3 * f + c] = rv;
+      z[3 * f + c] = zv;
+      p[3 * f + c] = zv;
+      acc[c] += rv * zv;
+      acc[3 + c] += rv * rv;
+    }
+  }
+  block_sum<6>(acc, s_w);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) part[(int64_t)blockIdx.x * 6 + k] = acc[k];
+  }
+}
+
+// one workgroup: the state before the first iteration
+__global__ __launch_bounds__(kThreads) void fair_init_state(const double* __restrict__ part_bb, const double* __restrict__ part_r,
+                                                            int nb, double tol, FairState* __restrict__ st) {
+  __shared__ double s_w[6][kThreads / 64];
+  double bb[3], t[6];
+  total_of<3>(part_bb, nb, bb, s_w);
+  total_of<6>(part_r, nb, t, s_w);
+  if (threadIdx.x != 0) return;
+  int all = 1;
+  for (int c = 0; c < 3; ++c) {
+    st->rz[c] = t[c];
+    st->rr[c] = t[3 + c];
+    st->bb[c] = bb[c];
+    st->thr[c] = (tol * tol) * bb[c];
+    st->frozen[c] = t[3 + c] <= st->thr[c];
+    all &= st->frozen[c];
+  }
+  st->all_frozen = all;
+  st->done_iter = all ? 0 : -1;
+}
+
+// alpha = r.z / p.q (0 for a frozen coordinate, which is left as it is); x += alpha p, r -= alpha q, z = r / diag
+__global__ __launch_bounds__(kThreads) void fair_update(const double* __restrict__ part_pq, int nb, const FairState* __restrict__ st,
+                                                        const double* __restrict__ p, const double* __restrict__ q,
+                                                        const double* __restrict__ diag, int64_t nf, int64_t chunk,
+                                                        double* __restrict__ x, double* __restrict__ r, double* __restrict__ z,
+                                                        double* __restrict__ part) {
+  __shared__ double s_w[6][kThreads / 64];
+  double pq[3], alpha[3];
+  bool frozen[3];
+  total_of<3>(part_pq, nb, pq, s_w);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    frozen[c] = st->frozen[c] != 0;
+    alpha[c] = frozen[c] ? 0.0 : st->rz[c] / pq[c];
+  }
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const int64_t base = (int64_t)blockIdx.x * chunk;
+  for (int64_t t = threadIdx.x; t < chunk; t += kThreads) {
+    const int64_t f = base + t;
+    if (f >= nf) break;
+    const double d = diag[f];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      double rv = r[3 * f + c], zv = z[3 * f + c];
+      if (!frozen[c]) {
+        x[3 * f + c] += alpha[c] * p[3 * f + c];
+        rv -= alpha[c] * q[3 * f + c];
+        zv = rv / d;
+        r[3 * f + c] = rv;
+        z[3 * f + c] = zv;
+      }
+      acc[c] += rv * zv;
+      acc[3 + c] += rv * rv;
+    }
+  }
+  block_sum<6>(acc, s_w);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) part[(int64_t)blockIdx.x * 6 + k] = acc[k];
+  }
+}
+
+// beta = r.z / (r.z before); a coordinate whose r.r <= tol^2 b.b is frozen from here on; p = z + beta p for the others.
+// Block 0 writes the next state; every block reads the current one.
+__global__ __launch_bounds__(kThreads) void fair_direction(const double* __restrict__ part_r, int nb, const FairState* __restrict__ cur,
+                                                           FairState* __restrict__ nxt, int64_t iter,
+                                                           const double* __restrict__ z, int64_t nf, int64_t chunk,
+                                                           double* __restrict__ p) {
+  __shared__ double s_w[6][kThreads / 64];
+  double t[6], beta[3];
+  bool was[3], frozen[3];
+  total_of<6>(part_r, nb, t, s_w);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    was[c] = cur->frozen[c] != 0;
+    frozen[c] = was[c] || t[3 + c] <= cur->thr[c];
+    beta[c] = frozen[c] ? 0.0 : t[c] / cur->rz[c];
+  }
+  const int64_t base = (int64_t)blockIdx.x * chunk;
+  for (int64_t u = threadIdx.x; u < chunk; u += kThreads) {
+    const int64_t f = base + u;
+    if (f >= nf) break;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (!frozen[c]) p[3 * f + c] = z[3 * f + c] + beta[c] * p[3 * f + c];
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    int all = 1;
+    for (int c = 0; c < 3; ++c) {
+      nxt->rz[c] = was[c] ? cur->rz[c] : t[c];
+      nxt->rr[c] = was[c] ? cur->rr[c] : t[3 + c];
+      nxt->bb[c] = cur->bb[c];
+      nxt->thr[c] = cur->thr[c];
+      nxt->frozen[c] = frozen[c];
+      all &= (int)frozen[c];
+    }
+    nxt->all_frozen = all;
+    nxt->done_iter = cur->done_iter >= 0 ? cur->done_iter : (all ? iter + 1 : -1);
+  }
+}
+
+// the free vertices of the result, rounded to float32 once
+__global__ void fair_store(const double* __restrict__ x, const int32_t* __restrict__ free_s, const int32_t* __restrict__ s_glob,
+                           int64_t nf, float* __restrict__ out) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  const int64_t g = s_glob[free_s[f]];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[3 * g + c] = (float)x[3 * f + c];
+}
+
+template <int NC>
+int apply_on(sg_fair* s, const double* p, double* q, bool dot, hipStream_t stream) {
+  fair_rows<NC><<<blocks_for(s->nS), kThreads, 0, stream>>>(s->rowptr.p, s->col_f.p, s->s_free.p, s->invd.p, p, s->nS, s->y.p,
+                                                            s->yw.p);
+  if (dot)
+    fair_cols<NC, true><<<s->nb, kThreads, 0, stream>>>(s->rowptr.p, s->col_s.p, s->free_s.p, s->y.p, s->yw.p, p, s->nf, s->chunk,
+                                                        q, s->part_a.p);
+  else
+    fair_cols<NC, false><<<s->nb, kThreads, 0, stream>>>(s->rowptr.p, s->col_s.p, s->free_s.p, s->y.p, s->yw.p, p, s->nf, s->chunk,
+                                                         q, nullptr);
+  SG_HIP_TRY(hipGetLastError());
+  return SG_OK;
+}
+
+}  // namespace
+
+void destroy_fair(sg_fair* s) { delete s; }
+
+void fair_query(const sg_fair* s, int64_t* info) {
+  info[0] = s->nf;
+  info[1] = s->nS;
+  info[2] = s->nnz;
+  info[3] = s->bad_vertex;
+  info[4] = s->bad_kind;
+  info[5] = s->nb;
+  info[6] = 4;                 // launches per iteration
+  info[7] = 0;
+}
+
+int fair_create(const int64_t* faces, int64_t F, int64_t V, const uint8_t* free, hipStream_t stream, sg_fair** out) {
+  const int64_t n_half = 3 * F, n_dir = 6 * F;
+  SG_REQUIRE(V < (int64_t)kNoVertex && n_dir < ((int64_t)1 << 31), "sg_fair_create: sizes must fit int32");
+  std::unique_ptr<sg_fair> s(new (std::nothrow) sg_fair);
+  SG_REQUIRE(s != nullptr, "sg_fair_create: out of host memory");
+  s->V = V;
+  if (V == 0) {
+    *out = s.release();
+    return SG_OK;
+  }
+  // the sorted distinct (source, neighbour) pairs of the whole mesh and their row bounds, as sg_smooth_create builds them
+  DeviceBuf<uint64_t> keys_a, keys_b, ukeys;
+  DeviceBuf<int32_t> counts, rowptr;
+  DeviceBuf<int> n_runs, flags;
+  DeviceBuf<char> temp;
+  int h_runs = 0, h_flags[4] = {0, 0, kNoVertex, kNoVertex};
+  SG_HIP_TRY(flags.alloc(4));
+  SG_HIP_TRY(hipMemsetAsync(flags.p, 0, 2 * sizeof(int), stream));
+  SG_HIP_TRY(hipMemsetAsync(flags.p + 2, 0x7f, 2 * sizeof(int), stream));
+  SG_HIP_TRY(rowptr.alloc(V + 1));
+  if (F > 0) {
+    SG_HIP_TRY(keys_a.alloc(n_dir));
+    SG_HIP_TRY(keys_b.alloc(n_dir));
+    SG_HIP_TRY(ukeys.alloc(n_dir));
+    SG_HIP_TRY(counts.alloc(n_dir));
+    SG_HIP_TRY(n_runs.alloc(1));
+    directed_keys<<<blocks_for(n_half), kThreads, 0, stream>>>(faces, n_half, V, keys_a.p, flags.p);
+    SG_HIP_TRY(hipGetLastError());
+    const int hi_bits = bits_for((uint64_t)V, 32);
+    const uint64_t* sorted = keys_b.p;
+    size_t t1 = 0, t2 = 0;
+    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, keys_a.p, keys_b.p, (int)n_dir, 0, 32 + hi_bits, stream));
+    SG_HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, sorted, ukeys.p, counts.p, n_runs.p, (int)n_dir, stream));
+    const size_t tb = t1 > t2 ? t1 : t2;
+    SG_HIP_TRY(temp.alloc(tb ? tb : 16));
+    SG_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(temp.p, t1, keys_a.p, keys_b.p, (int)n_dir, 0, 32 + hi_bits, stream));
+    SG_HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(temp.p, t2, sorted, ukeys.p, counts.p, n_runs.p, (int)n_dir, stream));
+    SG_HIP_TRY(hipMemcpyAsync(&h_runs, n_runs.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+    SG_HIP_TRY(hipMemcpyAsync(h_flags, flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    SG_HIP_TRY(hipStreamSynchronize(stream));
+    SG_REQUIRE(!h_flags[0], "sg_fair_create: face refers to a vertex outside [0, %lld)", (long long)V);
+    SG_REQUIRE(!h_flags[1], "sg_fair_create: degenerate face (repeated vertex)");
+    SG_REQUIRE(h_runs >= 0 && h_runs <= n_dir, "sg_fair_create: run count %d out of range", h_runs);
+  }
+  row_starts<<<blocks_for(V + 1), kThreads, 0, stream>>>(ukeys.p, (int64_t)h_runs, V, rowptr.p);
+  SG_HIP_TRY(hipGetLastError());
+
+  // S, the free list and the row lengths, then their exclusive sums: the compact numberings
+  DeviceBuf<int32_t> is_free, in_s, rowlen, f_idx, s_idx, out_ptr;
+  SG_HIP_TRY(is_free.alloc(V + 1));
+  SG_HIP_TRY(in_s.alloc(V + 1));
+  SG_HIP_TRY(rowlen.alloc(V + 1));
+  SG_HIP_TRY(f_idx.alloc(V + 1));
+  SG_HIP_TRY(s_idx.alloc(V + 1));
+  SG_HIP_TRY(out_ptr.alloc(V + 1));
+  fair_mark<<<blocks_for(V + 1), kThreads, 0, stream>>>(free, rowptr.p, ukeys.p, V, is_free.p, in_s.p, rowlen.p, flags.p + 2);
+  SG_HIP_TRY(hipGetLastError());
+  if (int rc = exclusive_sum(is_free.p, f_idx.p, V + 1, stream)) return rc;
+  if (int rc = exclusive_sum(in_s.p, s_idx.p, V + 1, stream)) return rc;
+  if (int rc = exclusive_sum(rowlen.p, out_ptr.p, V + 1, stream)) return rc;
+  int32_t h_nf = 0, h_ns = 0, h_nnz = 0;
+  SG_HIP_TRY(hipMemcpyAsync(&h_nf, f_idx.p + V, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipMemcpyAsync(&h_ns, s_idx.p + V, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipMemcpyAsync(&h_nnz, out_ptr.p + V, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipMemcpyAsync(h_flags + 2, flags.p + 2, sizeof(int), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipStreamSynchronize(stream));
+  SG_REQUIRE(h_nf >= 0 && h_nf <= h_ns && h_ns <= V && h_nnz >= 0 && h_nnz <= h_runs, "sg_fair_create: counts out of range");
+  s->nf = h_nf;
+  s->nS = h_ns;
+  s->nnz = h_nnz;
+  if (h_flags[2] != kNoVertex) {           // a free vertex without edges: nothing below is built
+    s->bad_vertex = h_flags[2];
+    s->bad_kind = 1;
+    *out = s.release();
+    return SG_OK;
+  }
+  if (h_nf == 0) {
+    *out = s.release();
+    return SG_OK;
+  }
+  const int64_t nf = s->nf, nS = s->nS;
+  const int64_t blocks = (nf + kThreads - 1) / kThreads;
+  s->nb = (int)(blocks < kMaxPartials ? blocks : kMaxPartials);
+  s->chunk = ((blocks + s->nb - 1) / s->nb) * kThreads;
+  SG_HIP_TRY(s->rowptr.alloc(nS + 1));
+  SG_HIP_TRY(s->col_g.alloc(s->nnz));
+  SG_HIP_TRY(s->col_f.alloc(s->nnz));
+  SG_HIP_TRY(s->col_s.alloc(s->nnz));
+  SG_HIP_TRY(s->s_glob.alloc(nS));
+  SG_HIP_TRY(s->s_free.alloc(nS));
+  SG_HIP_TRY(s->free_s.alloc(nf));
+  SG_HIP_TRY(s->invd.alloc(nS));
+  SG_HIP_TRY(s->diag.alloc(nf));
+  SG_HIP_TRY(s->x.alloc(3 * nf));
+  SG_HIP_TRY(s->r.alloc(3 * nf));
+  SG_HIP_TRY(s->z.alloc(3 * nf));
+  SG_HIP_TRY(s->p.alloc(3 * nf));
+  SG_HIP_TRY(s->q.alloc(3 * nf));
+  SG_HIP_TRY(s->y.alloc(3 * nS));
+  SG_HIP_TRY(s->yw.alloc(3 * nS));
+  SG_HIP_TRY(s->part_a.alloc(3 * (size_t)s->nb));
+  SG_HIP_TRY(s->part_b.alloc(6 * (size_t)s->nb));
+  SG_HIP_TRY(s->state.alloc(2));
+  fair_fill<<<blocks_for(V + 1), kThreads, 0, stream>>>(rowptr.p, ukeys.p, free, in_s.p, f_idx.p, s_idx.p, out_ptr.p, V,
+                                                        s->rowptr.p, s->col_g.p, s->col_f.p, s->col_s.p, s->s_glob.p, s->s_free.p,
+                                                        s->free_s.p, s->invd.p);
+  fair_diag<<<blocks_for(nf), kThreads, 0, stream>>>(s->rowptr.p, s->col_s.p, s->free_s.p, s->invd.p, nf, s->diag.p);
+  SG_HIP_TRY(hipGetLastError());
+
+  // A is SPD exactly when every class of free vertices has an edge to a fixed vertex
+  DeviceBuf<int32_t> parent, anchored;
+  SG_HIP_TRY(parent.alloc(nf));
+  SG_HIP_TRY(anchored.alloc(nf));
+  SG_HIP_TRY(hipMemsetAsync(anchored.p, 0, (size_t)nf * sizeof(int32_t), stream));
+  iota32<<<blocks_for(nf), kThreads, 0, stream>>>(parent.p, nf);
+  fair_unite<<<blocks_for(nf), kThreads, 0, stream>>>(s->rowptr.p, s->col_f.p, s->free_s.p, nf, parent.p);
+  flatten<<<blocks_for(nf), kThreads, 0, stream>>>(parent.p, nf);
+  fair_anchor<<<blocks_for(nf), kThreads, 0, stream>>>(s->rowptr.p, s->col_f.p, s->free_s.p, parent.p, nf, anchored.p);
+  fair_floating<<<blocks_for(nf), kThreads, 0, stream>>>(parent.p, anchored.p, s->free_s.p, s->s_glob.p, nf, flags.p + 2);
+  SG_HIP_TRY(hipGetLastError());
+  SG_HIP_TRY(hipMemcpyAsync(h_flags + 3, flags.p + 3, sizeof(int), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipStreamSynchronize(stream));        // the temporaries are freed on return
+  if (h_flags[3] != kNoVertex) {
+    s->bad_vertex = h_flags[3];
+    s->bad_kind = 2;
+  }
+  *out = s.release();
+  return SG_OK;
+}
+
+int fair_diagonal(const sg_fair* s, double* out, hipStream_t stream) {
+  SG_REQUIRE(s->bad_kind == 0, "sg_fair_diagonal: the system is singular (vertex %lld)", (long long)s->bad_vertex);
+  if (s->nf == 0) return SG_OK;
+  SG_HIP_TRY(hipMemcpyAsync(out, s->diag.p, (size_t)s->nf * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  return SG_OK;
+}
+
+int fair_apply(sg_fair* s, const double* p, double* q, hipStream_t stream) {
+  SG_REQUIRE(s->bad_kind == 0, "sg_fair_apply: the system is singular (vertex %lld)", (long long)s->bad_vertex);
+  if (s->nf == 0) return SG_OK;
+  return apply_on<1>(s, p, q, false, stream);
+}
+
+int fair_solve(sg_fair* s, const float* in, float* out, double tol, int64_t max_iter, int64_t check_every, hipStream_t stream,
+               int64_t* iterations, double* relres, int* converged) {
+  SG_REQUIRE(s->bad_kind == 0, "sg_fair_solve: the system is singular (vertex %lld)", (long long)s->bad_vertex);
+  *iterations = 0;
+  *converged = 1;
+  relres[0] = relres[1] = relres[2] = 0.0;
+  if (s->V == 0) return SG_OK;
+  if (in != out) SG_HIP_TRY(hipMemcpyAsync(out, in, (size_t)s->V * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
+  if (s->nf == 0) return SG_OK;
+  const int64_t nf = s->nf, nS = s->nS, chunk = s->chunk;
+  const int nb = s->nb;
+  const unsigned rows_grid = blocks_for(nS);
+  // b.b from the fixed positions alone, then the residual of x0 from all positions
+  fair_rows_vs<true><<<rows_grid, kThreads, 0, stream>>>(s->rowptr.p, s->col_g.p, s->col_f.p, s->s_glob.p, s->s_free.p, s->invd.p,
+                                                         in, nS, s->y.p, s->yw.p);
+  fair_cols<3, false><<<nb, kThreads, 0, stream>>>(s->rowptr.p, s->col_s.p, s->free_s.p, s->y.p, s->yw.p, nullptr, nf, chunk, s->q.p,
+                                                   nullptr);
+  fair_init_b<<<nb, kThreads, 0, stream>>>(s->q.p, nf, chunk, s->part_a.p);
+  fair_rows_vs<false><<<rows_grid, kThreads, 0, stream>>>(s->rowptr.p, s->col_g.p, s->col_f.p, s->s_glob.p, s->s_free.p, s->invd.p,
+                                                          in, nS, s->y.p, s->yw.p);
+  fair_cols<3, false><<<nb, kThreads, 0, stream>>>(s->rowptr.p, s->col_s.p, s->free_s.p, s->y.p, s->yw.p, nullptr, nf, chunk, s->q.p,
+                                                   nullptr);
+  fair_init_r<<<nb, kThreads, 0, stream>>>(s->q.p, s->diag.p, in, s->free_s.p, s->s_glob.p, nf, chunk, s->x.p, s->r.p, s->z.p,
+                                           s->p.p, s->part_b.p);
+  fair_init_state<<<1, kThreads, 0, stream>>>(s->part_a.p, s->part_b.p, nb, tol, s->state.p);
+  SG_HIP_TRY(hipGetLastError());
+  int cur = 0;
+  int64_t k = 0;
+  for (;;) {
+    if (k % check_every == 0) {
+      int32_t all = 0;
+      SG_HIP_TRY(hipMemcpyAsync(&all, &s->state.p[cur].all_frozen, sizeof(all), hipMemcpyDeviceToHost, stream));
+      SG_HIP_TRY(hipStreamSynchronize(stream));
+      if (all) break;
+    }
+    if (k >= max_iter) break;
+    if (int rc = apply_on<3>(s, s->p.p, s->q.p, true, stream)) return rc;
+    fair_update<<<nb, kThreads, 0, stream>>>(s->part_a.p, nb, s->state.p + cur, s->p.p, s->q.p, s->diag.p, nf, chunk, s->x.p,
+                                             s->r.p, s->z.p, s->part_b.p);
+    fair_direction<<<nb, kThreads, 0, stream>>>(s->part_b.p, nb, s->state.p + cur, s->state.p + (cur ^ 1), k, s->z.p, nf, chunk,
+                                                s->p.p);
+    SG_HIP_TRY(hipGetLastError());
+    cur ^= 1;
+    ++k;
+  }
+  fair_store<<<blocks_for(nf), kThreads, 0, stream>>>(s->x.p, s->free_s.p, s->s_glob.p, nf, out);
+  SG_HIP_TRY(hipGetLastError());
+  FairState h;
+  SG_HIP_TRY(hipMemcpyAsync(&h, s->state.p + cur, sizeof(h), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipStreamSynchronize(stream));
+  *converged = h.done_iter >= 0;
+  *iterations = h.done_iter >= 0 ? h.done_iter : k;
+  for (int c = 0; c < 3; ++c) relres[c] = h.bb[c] > 0.0 ? sqrt(h.rr[c] / h.bb[c]) : (h.rr[c] > 0.0 ? HUGE_VAL : 0.0);
+  return SG_OK;
+}
+
+}  // namespace sg

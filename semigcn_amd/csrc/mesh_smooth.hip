@@ -72,41 +72,7 @@ __global__ __launch_bounds__(kThreads) void edge_length_finish(const double* __r
 }
 
 // ---- plan ------------------------------------------------------------------------------------------------------------
-// Face-edge h = 3 f + i joins a = faces[f][i] and b = faces[f][(i+1)%3]; it puts b on a's list and a on b's: keys
-// (a << 32 | b) and (b << 32 | a).  flags[0]: vertex id out of range; flags[1]: degenerate face (repeated vertex).
-__global__ void directed_keys(const int64_t* __restrict__ faces, int64_t n_half, int64_t V, uint64_t* __restrict__ keys,
-                              int* __restrict__ flags) {
-  const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (h >= n_half) return;
-  const int64_t f = h / 3;
-  const int i = (int)(h - 3 * f);
-  const int64_t a = faces[3 * f + i], b = faces[3 * f + next3(i)];
-  uint64_t k0 = ~0ull, k1 = ~0ull;
-  if (a < 0 || a >= V || b < 0 || b >= V) {
-    flags[0] = 1;
-  } else {
-    if (a == b) flags[1] = 1;
-    k0 = ((uint64_t)a << 32) | (uint64_t)b;
-    k1 = ((uint64_t)b << 32) | (uint64_t)a;
-  }
-  keys[2 * h] = k0;
-  keys[2 * h + 1] = k1;
-}
-
-// rowptr[v] = first run whose source vertex is >= v (the runs are sorted by (source, neighbour))
-__global__ void row_starts(const uint64_t* __restrict__ ukeys, int64_t n, int64_t V, int32_t* __restrict__ rowptr) {
-  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v > V) return;
-  const uint64_t key = (uint64_t)v << 32;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (ukeys[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  rowptr[v] = (int32_t)lo;
-}
-
+// directed_keys and row_starts (mesh_common.h) give the sorted (source, neighbour) runs and the row bounds.
 // A run's length is k_ij.  flags[2]: an edge with more than 255 faces (the weight is kept in 8 bits).
 __global__ void row_weights(const uint64_t* __restrict__ ukeys, const int32_t* __restrict__ counts,
                             const int32_t* __restrict__ rowptr, int64_t V, int32_t* __restrict__ idx, uint8_t* __restrict__ w,

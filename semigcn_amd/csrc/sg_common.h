@@ -382,6 +382,14 @@ void fill_query(const sg_fill* s, int64_t* info);
 int fill_loops(const sg_fill* s, int64_t* loop_ptr_out, int64_t* loop_verts_out, hipStream_t stream);
 int fill_plan(sg_fill* s, int64_t max_hole_edges, hipStream_t stream, int64_t* n_new_vertices, int64_t* n_new_faces);
 int fill_emit(sg_fill* s, const float* vs, float* new_vs, int64_t* new_faces, uint8_t* filled_out, hipStream_t stream);
+// mesh_fair.hip
+int fair_create(const int64_t* faces, int64_t F, int64_t V, const uint8_t* free, hipStream_t stream, sg_fair** out);
+void destroy_fair(sg_fair* s);
+void fair_query(const sg_fair* s, int64_t* info);
+int fair_diagonal(const sg_fair* s, double* out, hipStream_t stream);
+int fair_apply(sg_fair* s, const double* p, double* q, hipStream_t stream);
+int fair_solve(sg_fair* s, const float* in, float* out, double tol, int64_t max_iter, int64_t check_every, hipStream_t stream,
+               int64_t* iterations, double* relres, int* converged);
 // mesh_parts.hip
 int parts_create(const int64_t* faces, int64_t F, int64_t V, int connectivity, hipStream_t stream, sg_parts** out);
 void destroy_parts(sg_parts* s);

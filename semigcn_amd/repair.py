@@ -150,7 +150,7 @@ def _grown(faces: torch.Tensor, flagged: torch.Tensor, num_vertices: int, grow: 
     return flagged
 
 
-def _loop(vs, faces, ids, grow, max_rounds, max_hole_edges, fair_steps, cut=False) -> Repaired:
+def _loop(vs, faces, ids, grow, max_rounds, max_hole_edges, fair_steps, cut=False, fair="laplacian") -> Repaired:
     """``cut``: a deletion may leave two fans hanging on one vertex; cut them apart (``manifold.split_nonmanifold``) before
     the largest component is taken, so that the boundary can always be ordered into loops."""
     from . import components, holes, manifold
@@ -170,13 +170,15 @@ def _loop(vs, faces, ids, grow, max_rounds, max_hole_edges, fair_steps, cut=Fals
         if kept.faces.shape[0] == 0:
             vs, faces = kept.vs, kept.faces
         else:
-            filled = holes.fill_holes((kept.vs, kept.faces), max_hole_edges=max_hole_edges, fair_steps=fair_steps)
+            filled = holes.fill_holes((kept.vs, kept.faces), max_hole_edges=max_hole_edges, fair_steps=fair_steps, fair=fair)
             vs, faces = filled.vs, filled.faces
             ids = torch.cat([ids, ids.new_full((vs.shape[0] - ids.shape[0],), -1)])
         rounds += 1
 
 
-def _check_loop_args(grow, max_rounds, max_hole_edges, fair_steps):
+def _check_loop_args(grow, max_rounds, max_hole_edges, fair_steps, fair="laplacian"):
+    if fair not in ("laplacian", "thin_plate"):
+        raise ValueError(f"remove_self_intersections: fair must be 'laplacian' or 'thin_plate', got {fair!r}")
     if int(grow) < 0:
         raise ValueError(f"remove_self_intersections: grow must be >= 0, got {grow}")
     if int(max_rounds) < 0:
@@ -189,18 +191,18 @@ def _check_loop_args(grow, max_rounds, max_hole_edges, fair_steps):
 
 
 def remove_self_intersections(mesh, grow: int = 1, max_rounds: int = 10, max_hole_edges: Optional[int] = None,
-                              fair_steps: int = prepare.SMOOTH_ITER) -> Repaired:
+                              fair_steps: int = prepare.SMOOTH_ITER, fair: str = "laplacian") -> Repaired:
     """The repair loop of the module docstring on ``mesh``.  A clean mesh comes back as it is (``rounds == 0``, the same
-    ``vs`` and ``faces`` bytes); ``max_rounds = 0`` only detects (``remaining = P``).  ``max_hole_edges`` and
-    ``fair_steps`` go to ``holes.fill_holes``."""
-    args = _check_loop_args(grow, max_rounds, max_hole_edges, fair_steps)
+    ``vs`` and ``faces`` bytes); ``max_rounds = 0`` only detects (``remaining = P``).  ``max_hole_edges``,
+    ``fair_steps`` and ``fair`` go to ``holes.fill_holes``."""
+    args = _check_loop_args(grow, max_rounds, max_hole_edges, fair_steps, fair)
     vs, faces = vs_faces(*check_mesh(mesh, dtypes=False))
     with capi._on_device(vs.device):
-        return _loop(vs, faces, torch.arange(vs.shape[0], dtype=torch.int64, device=vs.device), *args)
+        return _loop(vs, faces, torch.arange(vs.shape[0], dtype=torch.int64, device=vs.device), *args, fair=fair)
 
 
 def repair(mesh, grow: int = 1, max_rounds: int = 10, max_hole_edges: Optional[int] = None,
-           fair_steps: int = prepare.SMOOTH_ITER, make_manifold: bool = False):
+           fair_steps: int = prepare.SMOOTH_ITER, make_manifold: bool = False, fair: str = "laplacian"):
     """The whole ``MeshFix.repair()`` stage: keep the largest component, close the holes, remove the self-intersections.
     Returns ``(vs, faces, report)``: ``(vs, faces)`` is a valid ``initial`` for ``prepare.prepare_inputs``; ``report`` is
     the ``Repaired`` of the last step, its ``vertex_ids`` referring to the vertices of ``mesh``.  ``make_manifold``: run
@@ -208,9 +210,9 @@ def repair(mesh, grow: int = 1, max_rounds: int = 10, max_hole_edges: Optional[i
     then taken instead of refused -- and ``manifold.orient_faces`` once more after the holes are closed, since only then
     can the kept component be turned outward, and the bow-ties a round's deletion leaves are cut
     (``manifold.split_nonmanifold``) instead of stopping ``fill_holes``; ``vertex_ids`` then name the weld
-    representatives."""
+    representatives.  ``fair`` goes to every ``holes.fill_holes`` call."""
     from . import components, holes, manifold
-    args = _check_loop_args(grow, max_rounds, max_hole_edges, fair_steps)
+    args = _check_loop_args(grow, max_rounds, max_hole_edges, fair_steps, fair)
     vs, faces = vs_faces(*check_mesh(mesh, dtypes=False))
     with capi._on_device(vs.device):
         first = manifold.make_manifold((vs, faces)) if make_manifold else None
@@ -220,12 +222,12 @@ def repair(mesh, grow: int = 1, max_rounds: int = 10, max_hole_edges: Optional[i
         ids = kept.vertex_ids if first is None else first.vertex_ids[kept.vertex_ids]
         vs, faces = kept.vs, kept.faces
         if faces.shape[0]:
-            filled = holes.fill_holes((vs, faces), max_hole_edges=max_hole_edges, fair_steps=args[3])
+            filled = holes.fill_holes((vs, faces), max_hole_edges=max_hole_edges, fair_steps=args[3], fair=fair)
             vs, faces = filled.vs, filled.faces
             ids = torch.cat([ids, ids.new_full((vs.shape[0] - ids.shape[0],), -1)])
             if first is not None:
                 faces = manifold.orient_faces((vs, faces), outward=True).faces
-        report = _loop(vs, faces, ids, *args, cut=first is not None)
+        report = _loop(vs, faces, ids, *args, cut=first is not None, fair=fair)
         return report.vs, report.faces, report
 
 
