@@ -487,7 +487,8 @@ SG_API int sg_fill_emit(sg_fill* s, const float* vs, float* new_vs, int64_t* new
  *   |S|, entries of the rows' neighbour lists, the smallest offending vertex
  *   (-1: none), why (0: nothing; 1: the smallest free vertex without edges; 2:
  *   the smallest vertex of a free class without an edge to a fixed vertex),
- *   number of block partials per dot product, launches per iteration, 0.
+ *   number of block partials per dot product, launches per iteration, free
+ *   indices per block partial.
  * sg_fair_diagonal: copies diag(A)_i = 1 + sum_{j in N(i)} (1/d_j)^2, float64
  *   [nf] in free-list order, summed in ascending neighbour order, to a device
  *   array of the caller.  Asynchronous.
@@ -498,7 +499,8 @@ SG_API int sg_fill_emit(sg_fill* s, const float* vs, float* new_vs, int64_t* new
  *   bit.  Asynchronous; uses the plan's buffers: one call at a time per plan.
  * sg_fair_solve: from in float32 [V,3] to out float32 [V,3] (may be the same
  *   array).  x0 = the input positions; every coordinate has its own alpha, beta
- *   and stop test ||r||^2 <= tol^2 ||b||^2 on the recursive residual, and is
+ *   and stop test ||r||^2 <= tol^2 ||b||^2 on the recursive residual (a
+ *   coordinate with b = 0: tol^2 ||r0||^2, r0 the first residual), and is
  *   frozen (alpha = beta = 0) once it has met it; the solve ends when all three
  *   are frozen or after max_iter iterations.  The scalars stay on the device;
  *   the host reads one word every check_every iterations, which does not change
@@ -506,7 +508,8 @@ SG_API int sg_fill_emit(sg_fill* s, const float* vs, float* new_vs, int64_t* new
  *   partials added up in a fixed order: no floating-point atomics, two runs give
  *   identical bytes.  The free vertices are rounded to float32 once, every other
  *   vertex is copied bit for bit.  Returns (host) the iterations taken, the
- *   relative residual ||r|| / ||b|| per coordinate [3] and whether every
+ *   relative residual ||r|| / ||b|| (||r|| / ||r0|| where b = 0; 0 where r0 = 0
+ *   too) per coordinate [3] and whether every
  *   coordinate met its test; reaching max_iter is not an error.  Synchronises
  *   the stream.  tol < 0, max_iter < 0 or check_every < 1 gives SG_ERR_INVALID.
  * ------------------------------------------------------------------------- */

@@ -1597,8 +1597,8 @@ class FillPlan(_OwnedHandle):
 class FairPlan(_OwnedHandle):
     """Owns one sg_fair (csrc/mesh_fair.hip): the thin-plate system of the vertices ``free`` bool [V] of a triangle list
     (the rule is specified in semigcn_amd/holes.py, "Thin-plate fairing") and the vectors of its conjugate-gradient solve.
-    ``bad_vertex`` / ``bad_kind`` say why a system is singular; ``diagonal`` / ``apply`` / ``solve`` then raise.  One call
-    at a time per plan."""
+    ``bad_vertex`` / ``bad_kind`` say why a system is singular; ``diagonal`` / ``apply`` / ``solve`` then raise.
+    ``num_partials`` blocks each sum ``chunk`` consecutive free indices of a dot product.  One call at a time per plan."""
 
     _destroy = "sg_fair_destroy"
     _query_fn, _query_len = "sg_fair_query", 8
@@ -1615,7 +1615,7 @@ class FairPlan(_OwnedHandle):
         self._create("sg_fair_create", faces.device, _ptr(faces), faces.shape[0], self.num_vertices, _ptr(free), _stream(faces))
         info = self._query()
         self.num_free, self.num_rows, self.nnz, self.bad_vertex, self.bad_kind = (int(v) for v in info[:5])
-        self.num_partials, self.launches_per_iteration = int(info[5]), int(info[6])
+        self.num_partials, self.launches_per_iteration, self.chunk = int(info[5]), int(info[6]), int(info[7])
 
     @property
     def solvable(self) -> bool:

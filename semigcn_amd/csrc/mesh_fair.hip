@@ -35,7 +35,7 @@ constexpr int kMaxPartials = 1024;
 constexpr int kNoVertex = 0x7f7f7f7f;      // what a memset of 0x7f leaves: above every vertex id the plan takes
 
 struct FairState {
-  double rz[3], rr[3], bb[3], thr[3];   // r.z, r.r, b.b, tol^2 b.b per coordinate
+  double rz[3], rr[3], ref[3], thr[3];  // r.z, r.r, the reference norm (b.b, or r0.r0 where b.b is 0), tol^2 ref per coordinate
   int32_t frozen[3];
   int32_t all_frozen;                   // the word the host polls
   int64_t done_iter;                    // the iteration after which every coordinate was frozen; -1 until then
@@ -363,8 +363,8 @@ __global__ __launch_bounds__(kThreads) void fair_init_state(const double* __rest
   for (int c = 0; c < 3; ++c) {
     st->rz[c] = t[c];
     st->rr[c] = t[3 + c];
-    st->bb[c] = bb[c];
-    st->thr[c] = (tol * tol) * bb[c];
+    st->ref[c] = bb[c] > 0.0 ? bb[c] : t[3 + c];       // b = 0: the residual is measured against the first one
+    st->thr[c] = (tol * tol) * st->ref[c];
     st->frozen[c] = t[3 + c] <= st->thr[c];
     all &= st->frozen[c];
   }
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(kThreads) void fair_update(const double* __restrict
   }
 }
 
-// beta = r.z / (r.z before); a coordinate whose r.r <= tol^2 b.b is frozen from here on; p = z + beta p for the others.
+// beta = r.z / (r.z before); a coordinate whose r.r <= tol^2 ref is frozen from here on; p = z + beta p for the others.
 // Block 0 writes the next state; every block reads the current one.
 __global__ __launch_bounds__(kThreads) void fair_direction(const double* __restrict__ part_r, int nb, const FairState* __restrict__ cur,
                                                            FairState* __restrict__ nxt, int64_t iter,
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(kThreads) void fair_direction(const double* __restr
     for (int c = 0; c < 3; ++c) {
       nxt->rz[c] = was[c] ? cur->rz[c] : t[c];
       nxt->rr[c] = was[c] ? cur->rr[c] : t[3 + c];
-      nxt->bb[c] = cur->bb[c];
+      nxt->ref[c] = cur->ref[c];
       nxt->thr[c] = cur->thr[c];
       nxt->frozen[c] = frozen[c];
       all &= (int)frozen[c];
@@ -490,7 +490,7 @@ void fair_query(const sg_fair* s, int64_t* info) {
   info[4] = s->bad_kind;
   info[5] = s->nb;
   info[6] = 4;                 // launches per iteration
-  info[7] = 0;
+  info[7] = s->chunk;          // indices per block partial
 }
 
 int fair_create(const int64_t* faces, int64_t F, int64_t V, const uint8_t* free, hipStream_t stream, sg_fair** out) {
@@ -688,7 +688,7 @@ int fair_solve(sg_fair* s, const float* in, float* out, double tol, int64_t max_
   SG_HIP_TRY(hipStreamSynchronize(stream));
   *converged = h.done_iter >= 0;
   *iterations = h.done_iter >= 0 ? h.done_iter : k;
-  for (int c = 0; c < 3; ++c) relres[c] = h.bb[c] > 0.0 ? sqrt(h.rr[c] / h.bb[c]) : (h.rr[c] > 0.0 ? HUGE_VAL : 0.0);
+  for (int c = 0; c < 3; ++c) relres[c] = h.ref[c] > 0.0 ? sqrt(h.rr[c] / h.ref[c]) : 0.0;      // ref = 0: b = 0 and r0 = 0
   return SG_OK;
 }
 

@@ -59,8 +59,11 @@ leave the border along the scan's tangent instead (a cap cut from a sphere comes
   float64, from ``x0`` = the input positions (for ``fill_holes``: the raw construction).  ``||b||^2`` comes from
   ``M^T M`` applied to the positions with the free ones taken as 0, the first residual ``r0 = -M^T M x`` from all
   positions.  Each coordinate has its own ``alpha``, ``beta`` and stop test on the recursive residual,
-  ``||r||^2 <= tol^2 ||b||^2`` (a coordinate with ``b = 0`` and ``r0 = 0`` stops at once); a coordinate that has met it is
-  frozen -- its ``alpha`` and ``beta`` are 0 from then on -- so the result does not depend on how often the host looks.
+  ``||r||^2 <= tol^2 ||b||^2``.  A coordinate with ``b.b = 0`` -- every fixed vertex its rows reach has that coordinate
+  exactly 0 -- is measured against its first residual instead, ``||r||^2 <= tol^2 ||r0||^2``, and its
+  ``relative_residual`` is ``||r|| / ||r0||``; with ``r0 = 0`` too it stops at once and reports 0.  A coordinate with
+  ``b.b > 0`` is tested against ``tol^2 ||b||^2`` exactly.  A coordinate that has met its test is frozen -- its
+  ``alpha`` and ``beta`` are 0 from then on -- so the result does not depend on how often the host looks.
   The solve ends when all three are frozen or after ``max_iter`` iterations: a cap that is reported
   (``converged = False``), not an error.  The result is rounded to float32 once; fixed vertices are copied bit for bit.
 * Arithmetic: ``A p`` is two gathers, ``y_i = p_i - (1 / d_i) s_i`` over ``S`` with ``s_i`` the sum of the free ``p_j``,
@@ -180,7 +183,7 @@ def fair_thin_plate(vs, faces, free, tol: float = 1e-10, max_iter: int = 10000, 
                     return_info: bool = False):
     """float32 [V, 3]: ``vs`` with the vertices ``free`` bool [V] at the minimiser of the thin-plate energy of the module
     docstring and every other vertex bit for bit; any mesh, any mask.  ``return_info``: also a dict with ``iterations``,
-    the per-coordinate ``relative_residual`` (``||r|| / ||b||``), ``converged`` and ``n_free``.  ``max_iter`` is a cap that
+    the per-coordinate ``relative_residual`` (``||r|| / ||b||``; ``||r|| / ||r0||`` where ``b = 0``), ``converged`` and ``n_free``.  ``max_iter`` is a cap that
     is reported (``converged`` False), not an error; the host looks at the device's stop flag every ``check_every``
     iterations, which does not change the result.  An empty ``free`` returns a copy.  ``ValueError`` for a mask of the
     wrong length and for a singular system (it names the vertex)."""

@@ -8,6 +8,19 @@ mask of the inserted vertices.  Everything is computed once and handed out read-
   e  a 14 x 9 grid with a hole of 12 edges next to one of 18 that ``max_hole_edges = 12`` leaves open (and so the outer
      border): rows of S one edge from a border
   f  a 9 x 9 grid whose hole has an ear: a loop vertex with one mesh face, valence 3 once the patch is in
+
+The second family (``masked``) has no fill: a mesh, a mask of the caller's and start positions off the minimiser.
+
+  sweep<k>    64 x 64 grid with a smooth height; free = the first k vertices (ascending id) of the disc of radius 20.3
+              round the grid's centre, k in SWEEP: one wavefront, one block and one partial more or less than full
+  disc        that whole disc: 1288 free vertices, six blocks, the last one partial
+  blocks      861 x 861 grid; free where i % 5 and j % 5 are both in {1, 2, 3}: 266 256 free vertices (more than 1024
+              blocks of 256) in 29 584 classes of 9 that share no row, so A is block diagonal (``blocks_exact``)
+  sphere_mask, grid_mask      a seeded 30 % mask on icosphere(2) and on an open 12 x 12 grid, border vertices included
+  wheel_hub, wheel_rim        a wheel of 40 spokes with the hub free (valence 40), and with the rim free (valence 3)
+  soup, soup_clean            a grid with a fin (one edge with three faces); the soup repeats faces, some of them reversed
+  plane_off, plane_in         24 x 24 grid in z = 0, 232 free vertices in a disc, started 0.3 off their places in all three
+                              coordinates (b = 0 but r0 != 0 in z), and in x and y only (b = 0 and r0 = 0 in z)
 """
 from __future__ import annotations
 
@@ -202,3 +215,155 @@ def system(name) -> FO.System:
 
 
 NAMES = ("a", "b", "c", "d", "e", "f")
+
+
+# ---- meshes with a mask of the caller's ----------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Masked:
+    vs: np.ndarray                   # float32 [V, 3]
+    faces: np.ndarray                # int64 [F, 3]
+    free: np.ndarray                 # bool [V]
+
+
+SWEEP = (63, 64, 65, 255, 256, 257, 513, 1025)
+BLOCKS_N, BLOCKS_PERIOD = 861, 5
+MASKS = ("sphere_mask", "grid_mask", "wheel_hub", "wheel_rim", "soup")
+PLANES = ("plane_off", "plane_in")
+SMALL = tuple(f"sweep{k}" for k in SWEEP) + ("disc",) + MASKS + ("soup_clean",) + PLANES      # within reach of FO.System
+
+
+def grid_faces(n, m):
+    """the faces of ``grid(n, m)``, without the loop"""
+    a, b = np.meshgrid(np.arange(n - 1), np.arange(m - 1), indexing="ij")
+    v00 = (a * m + b).ravel()
+    v10, v11, v01 = v00 + m, v00 + m + 1, v00 + 1
+    return np.stack([np.stack([v00, v10, v11], 1), np.stack([v00, v11, v01], 1)], 1).reshape(-1, 3).astype(np.int64)
+
+
+def height_grid(n, amplitude):
+    """n x n grid at integer x, y with the height ``amplitude (sin(3.1 i / n) cos(2.3 j / n) + 1.5)``"""
+    i, j = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    i, j = i.ravel().astype(np.float64), j.ravel().astype(np.float64)
+    z = amplitude * (np.sin(3.1 * i / n) * np.cos(2.3 * j / n) + 1.5)
+    return np.stack([i, j, z], 1), grid_faces(n, n)
+
+
+def centre_disc(n, radius):
+    i, j = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    return ((i - (n - 1) / 2) ** 2 + (j - (n - 1) / 2) ** 2 <= radius * radius).ravel()
+
+
+def _masked(vs, faces, free, noise=0.0, seed=0, columns=(0, 1, 2)):
+    """The free vertices moved by seeded uniform noise of that size in ``columns``; everything rounded to float32 once."""
+    vs = np.array(vs, np.float64)
+    free = np.asarray(free, bool)
+    if noise:
+        step = np.random.default_rng(seed).uniform(-noise, noise, (int(free.sum()), 3))
+        for c in columns:
+            vs[free, c] += step[:, c]
+    out = Masked(np.ascontiguousarray(vs.astype(np.float32)), np.ascontiguousarray(np.asarray(faces, np.int64)), free)
+    for a in (out.vs, out.faces, out.free):
+        a.setflags(write=False)
+    return out
+
+
+def wheel(spokes):
+    """hub 0 above a rim 1 .. spokes that undulates round (1.5, 1, 1): no coordinate of a minimiser is near 0, where the
+    direct solve's own rounding would be all there is to compare with; faces (hub, k, k + 1)"""
+    a = 2 * np.pi * np.arange(spokes) / spokes
+    rim = np.stack([1.5 + np.cos(a), 1.0 + np.sin(a), 1.0 + 0.2 * np.sin(3 * a)], 1)
+    k = np.arange(spokes)
+    faces = np.stack([np.zeros(spokes, np.int64), 1 + k, 1 + (k + 1) % spokes], 1)
+    return np.concatenate([[[1.625, 0.75, 1.5]], rim], 0), faces
+
+
+def fin_grid():
+    """7 x 7 grid with a height, and one more face on the interior edge (3, 3)-(4, 4): that edge has three faces"""
+    vs, faces = height_grid(7, 0.5)
+    vs = np.concatenate([vs, [[3.4, 3.6, 2.0]]], 0)
+    return vs, np.concatenate([faces, [[3 * 7 + 3, 4 * 7 + 4, 49]]], 0)
+
+
+@functools.lru_cache(maxsize=None)
+def masked(name) -> Masked:
+    if name.startswith("sweep") or name == "disc":
+        vs, faces = height_grid(64, 4.0)
+        disc = centre_disc(64, 20.3)
+        k = int(disc.sum()) if name == "disc" else int(name[5:])
+        free = np.zeros(64 * 64, bool)
+        free[np.flatnonzero(disc)[:k]] = True
+        return _masked(vs, faces, free, 0.3, seed=k)
+    if name == "blocks":
+        n, q = BLOCKS_N, BLOCKS_PERIOD
+        vs, faces = height_grid(n, 4.0)
+        i, j = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+        free = (np.isin(i % q, (1, 2, 3)) & np.isin(j % q, (1, 2, 3))).ravel()
+        return _masked(vs, faces, free, 0.3, seed=q)
+    if name == "sphere_mask":
+        vs, faces = icosphere(2)
+        return _masked(vs, faces, np.random.default_rng(21).random(len(vs)) < 0.3, 0.1, seed=22)
+    if name == "grid_mask":
+        vs, faces = height_grid(12, 1.0)
+        return _masked(vs, faces, np.random.default_rng(23).random(144) < 0.3, 0.3, seed=24)
+    if name in ("wheel_hub", "wheel_rim"):
+        vs, faces = wheel(40)
+        free = np.arange(41) == 0
+        return _masked(vs, faces, free if name == "wheel_hub" else ~free, 0.1, seed=25)
+    if name in ("soup", "soup_clean"):
+        vs, faces = fin_grid()
+        free = np.zeros(50, bool)
+        free[[2 * 7 + 2, 2 * 7 + 3, 3 * 7 + 3, 4 * 7 + 4, 4 * 7 + 3, 49]] = True        # both ends of the fin's edge, and its tip
+        if name == "soup":
+            rng = np.random.default_rng(26)
+            again, back = rng.choice(len(faces), 9, replace=False), rng.choice(len(faces), 7, replace=False)
+            faces = np.concatenate([faces, faces[again], faces[back][:, ::-1], faces[-1:], faces[-1:, ::-1]], 0)
+            faces = faces[rng.permutation(len(faces))]
+        return _masked(vs, faces, free, 0.3, seed=27)
+    if name in PLANES:
+        vs, faces = grid(24, 24)
+        return _masked(vs, faces, centre_disc(24, 8.6), 0.3, seed=28, columns=(0, 1, 2) if name == "plane_off" else (0, 1))
+    raise KeyError(name)
+
+
+@functools.lru_cache(maxsize=None)
+def table(name) -> FO.Table:
+    c = masked(name) if name not in NAMES else case(name)
+    return FO.Table(c.faces, len(c.vs))
+
+
+@functools.lru_cache(maxsize=None)
+def masked_system(name) -> FO.System:
+    assert name in SMALL
+    c = masked(name)
+    return FO.System(c.vs, c.faces, c.free)
+
+
+@dataclass(frozen=True)
+class BlocksExact:
+    A: np.ndarray                    # float64 [B, 9, 9]  the diagonal blocks of A
+    rows: np.ndarray                 # int64 [B, 9]       their free indices
+    b: np.ndarray                    # float64 [nf, 3]
+    x: np.ndarray                    # float64 [nf, 3]    the solution of every block
+    min_eig: float                   # the smallest eigenvalue over all blocks
+
+
+@functools.lru_cache(maxsize=None)
+def blocks_exact() -> BlocksExact:
+    """The blocks fixture solved class by class.  Two free vertices couple in A exactly when a row holds both, and no row
+    of this mask reaches two classes, so ``A`` applied to the indicator of one of the nine places of a class, read at the
+    class's own vertices, is a column of that class's 9 x 9 block."""
+    c, t = masked("blocks"), table("blocks")
+    n, q = BLOCKS_N, BLOCKS_PERIOD
+    ids = np.flatnonzero(c.free)
+    i, j = ids // n, ids % n
+    place = (i % q - 1) * 3 + (j % q - 1)
+    block = (i // q) * ((n + q - 1) // q) + j // q
+    order = np.lexsort((place, block))
+    rows = order.reshape(-1, 9)
+    assert (block[rows] == block[rows[:, :1]]).all() and (place[rows] == np.arange(9)).all()
+    cols = FO.apply_table(t, c.free, (place[:, None] == np.arange(9)).astype(np.float64))       # [nf, 9]
+    A = cols[rows]                                           # A[B, r, k] = (A e_k)[row r of B]
+    b = -FO.normal_rows(t, c.free, c.vs, True)
+    x = np.empty_like(b)
+    x[rows.reshape(-1)] = np.linalg.solve(A, b[rows]).reshape(-1, 3)
+    return BlocksExact(A, rows, b, x, float(np.linalg.eigvalsh(0.5 * (A + A.transpose(0, 2, 1))).min()))
