@@ -395,6 +395,74 @@ SG_API int sg_surface_self_pairs(const sg_surface* s, const float* vs, const int
                                  const int64_t* offsets, int64_t n_pairs, int64_t* pairs, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Area-weighted surface samples and the reductions of the two-sided sampled
+ * distance (Hausdorff, Chamfer, normal consistency): what MeshLab's
+ * hausdorff_distance filter is used for, and what the reference's one-sided
+ * vertex mean (above) cannot see.  The sampling rule -- integer weights,
+ * Philox4x32-10, a binary search in an integer prefix sum, 24-bit
+ * barycentrics -- is specified in semigcn_amd/evaluate.py ("Sampling rule");
+ * every choice in it is integer arithmetic, so two runs, and any other
+ * implementation of the rule, give identical bytes.  csrc/mesh_sample.hip.
+ *
+ * Limits: F < 2^31 and N < 2^31 per call.  A null pointer, a negative size or
+ * a size beyond these gives SG_ERR_INVALID before the device is touched;
+ * N == 0 returns SG_OK without a launch (and writes nothing).  A face below
+ * 2^-31 of the largest area has weight 0 and is never drawn.
+ *
+ * sg_sampler_create: the plan of one surface (vs float32 [V,3], faces int64
+ *   [F,3], face_mask_or_null uint8 [F], device): the face weights w uint64 [F]
+ *   (w_f < 2^31, proportional to the face's area; 0 where the mask byte is 0)
+ *   and cdf uint64 [F+1], their exclusive prefix sum.  The plan owns a copy of
+ *   the triangles; vs / faces / the mask are borrowed until the call returns.
+ *   A face index outside [0, V) or a face whose squared normal is not finite
+ *   gives SG_ERR_INVALID; the index is checked on the device before any vertex
+ *   is read through it.  F == 0 or V == 0 gives SG_ERR_INVALID.  Synchronises
+ *   the stream.
+ * sg_sampler_query: info[4] (host) = (W = cdf[F], the scale exponent s of the
+ *   rule, the number of faces with weight 0 -- masked ones included --, F).
+ * sg_sampler_export: copies w [F] and cdf [F+1] (device; either may be null).
+ * sg_sampler_locate: face[i] = the f with cdf[f] <= t[i] < cdf[f+1], for N
+ *   offsets t uint64 [N] < W (device): the binary search of a draw alone.
+ *   t[i] >= W is not an error and gives F - 1.
+ * sg_sampler_draw: draws k = offset .. offset + N - 1 of the stream `seed`:
+ *   points float32 [N,3], face int32 [N], bary_or_null int32 [N,3] = (w0, a, b)
+ *   out of 2^24, index_or_null int64 [N] = k.  order SG_SAMPLE_ORDER_FACE: rows
+ *   sorted by (face, k) (one stable radix sort); SG_SAMPLE_ORDER_DRAW: row i is
+ *   draw offset + i.  A draw depends on (seed, k) and the plan only, so chunks
+ *   of a stream concatenate.  W == 0 with N > 0 gives SG_ERR_INVALID.
+ *   Asynchronous.
+ * sg_distance_stats: out (device, 5 doubles) = (max |d|, sum |d|, sum d^2,
+ *   count of |d| <= tau, rows skipped) over dist float32 [N]; a row with an
+ *   infinite d (a query point without a closest point) is skipped and counted
+ *   in out[4].  partial: device scratch of 5 * SG_REDUCE_BLOCKS doubles.  Block
+ *   partials over fixed runs of consecutive indices, added in block order: no
+ *   floating-point atomics, deterministic.  Asynchronous.
+ * sg_normal_agreement: out (device, 2 doubles) = (sum |cos|, count) over the N
+ *   pairs (face_a[i] of surface a, face_b[i] of surface b), cos = n_a . n_b /
+ *   sqrt(nn_a nn_b) in float64 on the float32 vertices.  A pair with a negative
+ *   face id, face id 0x7fffffff (sg_surface_query's "no face") or a zero normal
+ *   on either side is skipped.  The face ids must be those of the two
+ *   surfaces: they are not checked against F.  partial: device scratch of
+ *   3 * SG_REDUCE_BLOCKS doubles.  Deterministic as above.  Asynchronous.
+ * ------------------------------------------------------------------------- */
+#define SG_REDUCE_BLOCKS 1024
+#define SG_SAMPLE_ORDER_FACE 0
+#define SG_SAMPLE_ORDER_DRAW 1
+typedef struct sg_sampler sg_sampler;
+SG_API int sg_sampler_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, const uint8_t* face_mask_or_null,
+                             void* stream, sg_sampler** out);
+SG_API int sg_sampler_destroy(sg_sampler* s);
+SG_API int sg_sampler_query(const sg_sampler* s, int64_t* info);
+SG_API int sg_sampler_export(const sg_sampler* s, uint64_t* w_or_null, uint64_t* cdf_or_null, void* stream);
+SG_API int sg_sampler_locate(const sg_sampler* s, const uint64_t* t, int64_t N, int32_t* face, void* stream);
+SG_API int sg_sampler_draw(const sg_sampler* s, uint64_t seed, uint64_t offset, int64_t N, int order, float* points,
+                           int32_t* face, int32_t* bary_or_null, int64_t* index_or_null, void* stream);
+SG_API int sg_distance_stats(const float* dist, int64_t N, float tau, double* partial, double* out, void* stream);
+SG_API int sg_normal_agreement(const float* vs_a, const int64_t* faces_a, const int32_t* face_a, const float* vs_b,
+                               const int64_t* faces_b, const int32_t* face_b, int64_t N, double* partial, double* out,
+                               void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Network inputs from a remeshed scan -- replaces the tail of
  * preprocess/prepare.py: edge_based_scaling (:48-52) and smooth (:110-114,
  * pymeshlab's laplacian_smooth with stepsmoothnum=30, cotangentweight=False).

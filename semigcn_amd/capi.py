@@ -201,6 +201,16 @@ _SIGNATURES = {
     "sg_surface_self_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "sg_mesh_distance_reduce": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                         c_void_p]),
+    "sg_sampler_create": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "sg_sampler_destroy": (c_int, [c_void_p]),
+    "sg_sampler_query": (c_int, [c_void_p, POINTER(c_int64)]),
+    "sg_sampler_export": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_sampler_locate": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "sg_sampler_draw": (c_int, [c_void_p, ctypes.c_uint64, ctypes.c_uint64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    "sg_distance_stats": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
+    "sg_normal_agreement": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                    c_void_p]),
     "sg_edge_length_blocks": (c_int64, [c_int64]),
     "sg_mean_edge_length": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sg_smooth_create": (c_int, [c_void_p, c_int64, c_int64, c_void_p, POINTER(c_void_p)]),
@@ -316,7 +326,9 @@ def load():
 def _check(rc: int, what: str):
     if rc != 0:
         msg = load().sg_last_error()
-        raise SemigcnLibraryError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
+        err = SemigcnLibraryError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
+        err.code = rc               # SG_ERR_*: a caller may tell a refused argument (-1) from a device error
+        raise err
 
 
 def _require_device(t: torch.Tensor, name: str):
@@ -1474,6 +1486,129 @@ def mesh_distance_reduce(q: torch.Tensor, gt_vs: torch.Tensor, q_org: Optional[t
         _check(load().sg_mesh_distance_reduce(_ptr(q), _ptr(q_org), float(eps), _ptr(hole), _ptr(gt_vs), N, _ptr(hole_out),
                                               _ptr(out), _stream(q)), "sg_mesh_distance_reduce")
     return out, hole_out
+
+
+SAMPLE_ORDERS = {"face": 0, "draw": 1}       # SG_SAMPLE_ORDER_*
+REDUCE_BLOCKS = 1024                         # SG_REDUCE_BLOCKS
+NO_FACE = 0x7FFFFFFF                         # sg_surface_query's face of a point without a closest point
+
+
+class SamplerPlan(_OwnedHandle):
+    """Owns one sg_sampler (csrc/mesh_sample.hip): the integer face weights of one surface and their prefix sum (the rule
+    is specified in semigcn_amd/evaluate.py, "Sampling rule"), and a copy of its triangles.  ``total_weight`` is W,
+    ``n_zero_weight`` the number of faces that are never drawn (zero or negligible area, or masked out).  ``ValueError``
+    for what the library refuses about the mesh itself: a face index outside [0, V), a non-finite vertex of a face."""
+
+    _destroy = "sg_sampler_destroy"
+    _query_fn, _query_len = "sg_sampler_query", 4
+
+    def __init__(self, vs: torch.Tensor, faces: torch.Tensor, face_mask: Optional[torch.Tensor] = None):
+        _require_device(vs, "vs")
+        _require_device(faces, "faces")
+        vs, faces = _vs_arg(vs).contiguous(), _faces_arg(faces)
+        if faces.device != vs.device:
+            raise SemigcnLibraryError(f"faces on {faces.device}, vs on {vs.device}")
+        if vs.shape[0] == 0 or faces.shape[0] == 0:
+            raise ValueError(f"SamplerPlan: need at least one face and one vertex, got F = {faces.shape[0]}, V = {vs.shape[0]}")
+        if face_mask is not None:
+            _require_device(face_mask, "face_mask")
+            if face_mask.numel() != faces.shape[0] or face_mask.device != vs.device:
+                raise ValueError(f"face_mask must hold {faces.shape[0]} entries on {vs.device}, got {tuple(face_mask.shape)} "
+                                 f"on {face_mask.device}")
+            face_mask = (face_mask.reshape(-1) != 0).contiguous()            # bool: one byte per face, 0 / 1
+        self.device, self.num_vertices, self.num_faces = vs.device, vs.shape[0], faces.shape[0]
+        try:
+            self._create("sg_sampler_create", vs.device, _ptr(vs), vs.shape[0], _ptr(faces), faces.shape[0], _ptr(face_mask),
+                         _stream(vs))
+        except SemigcnLibraryError as e:
+            if getattr(e, "code", None) == -1:      # SG_ERR_INVALID: the mesh, not the device
+                raise ValueError(str(e)) from None
+            raise
+        info = self._query()
+        self.total_weight, self.scale_exponent, self.n_zero_weight = int(info[0]), int(info[1]), int(info[2])
+
+    def export(self):
+        """(w [F], cdf [F + 1]) on the plan's device: the library's uint64 as int64 tensors (w < 2^31, cdf < 2^62)."""
+        self._open()
+        w = torch.empty(self.num_faces, dtype=torch.int64, device=self.device)
+        cdf = torch.empty(self.num_faces + 1, dtype=torch.int64, device=self.device)
+        with _on_device(self.device):
+            _check(load().sg_sampler_export(self._h, _ptr(w), _ptr(cdf), _raw_stream_of(self.device)), "sg_sampler_export")
+        return w, cdf
+
+    def locate(self, t: torch.Tensor) -> torch.Tensor:
+        """face int32 [N]: the f with cdf[f] <= t < cdf[f + 1] for offsets t int64 [N] in [0, ``total_weight``)."""
+        _require_device(t, "t")
+        if t.dtype != torch.int64 or t.dim() != 1 or t.device != self.device:
+            raise SemigcnLibraryError(f"t must be int64 [N] on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        self._open()
+        t = t.contiguous()
+        face = torch.empty(t.shape[0], dtype=torch.int32, device=self.device)
+        with _on_device(self.device):
+            _check(load().sg_sampler_locate(self._h, _ptr(t), t.shape[0], _ptr(face), _stream(t)), "sg_sampler_locate")
+        return face
+
+    def draw(self, n: int, seed: int = 0, offset: int = 0, order: str = "face"):
+        """(points float32 [n, 3], face int32 [n], bary int32 [n, 3], index int64 [n]): draws ``offset .. offset + n - 1``
+        of the stream ``seed``, sorted by (face, index) or, with ``order="draw"``, by index."""
+        n, seed, offset = int(n), int(seed), int(offset)
+        if order not in SAMPLE_ORDERS:
+            raise ValueError(f"order must be one of {tuple(SAMPLE_ORDERS)}, got {order!r}")
+        if n < 0 or n >= 1 << 31:
+            raise ValueError(f"n must be in [0, 2^31), got {n}")
+        if not (0 <= seed < 1 << 64 and 0 <= offset and offset + n <= 1 << 64):
+            raise ValueError(f"seed and the draw indices offset .. offset + n must fit 64 bits, got seed {seed}, offset {offset}")
+        if n > 0 and self.total_weight == 0:
+            raise ValueError("every face has weight 0 (zero area, or masked out): there is nothing to draw from")
+        self._open()
+        points = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        face = torch.empty(n, dtype=torch.int32, device=self.device)
+        bary = torch.empty((n, 3), dtype=torch.int32, device=self.device)
+        index = torch.empty(n, dtype=torch.int64, device=self.device)
+        with _on_device(self.device):
+            _check(load().sg_sampler_draw(self._h, seed, offset, n, SAMPLE_ORDERS[order], _ptr(points), _ptr(face), _ptr(bary),
+                                          _ptr(index), _raw_stream_of(self.device)), "sg_sampler_draw")
+        return points, face, bary, index
+
+
+def distance_stats(dist: torch.Tensor, tau: Optional[float] = None) -> torch.Tensor:
+    """float64 [5] on the device: (max |d|, sum |d|, sum d^2, count of |d| <= tau, rows skipped because d is infinite)
+    over dist float32 [N] (sg_distance_stats: a fixed summation order).  ``tau`` None counts nothing."""
+    _require_device(dist, "dist")
+    if dist.dtype != torch.float32 or dist.dim() != 1:
+        raise SemigcnLibraryError(f"dist must be float32 [N], got {dist.dtype} {tuple(dist.shape)}")
+    dist = dist.contiguous()
+    out = torch.zeros(5, dtype=torch.float64, device=dist.device)
+    if dist.shape[0]:
+        part = torch.empty(5 * REDUCE_BLOCKS, dtype=torch.float64, device=dist.device)
+        with _on_device(dist.device):
+            _check(load().sg_distance_stats(_ptr(dist), dist.shape[0], -1.0 if tau is None else float(tau), _ptr(part), _ptr(out),
+                                            _stream(dist)), "sg_distance_stats")
+    return out
+
+
+def normal_agreement(vs_a: torch.Tensor, faces_a: torch.Tensor, face_a: torch.Tensor, vs_b: torch.Tensor, faces_b: torch.Tensor,
+                     face_b: torch.Tensor) -> torch.Tensor:
+    """float64 [2] on the device: (sum |cos|, count) over the pairs of faces (face_a[i] of a, face_b[i] of b), int32 [N]
+    each (sg_normal_agreement).  The ids must be faces of the two meshes, negative or ``NO_FACE`` to skip a pair."""
+    ts = ((vs_a, "vs_a"), (faces_a, "faces_a"), (face_a, "face_a"), (vs_b, "vs_b"), (faces_b, "faces_b"), (face_b, "face_b"))
+    for t, name in ts:
+        _require_device(t, name)
+        if t.device != vs_a.device:
+            raise SemigcnLibraryError(f"{name} on {t.device}, vs_a on {vs_a.device}")
+    vs_a, vs_b = _vs_arg(vs_a).contiguous(), _vs_arg(vs_b).contiguous()
+    faces_a, faces_b = _faces_arg(faces_a), _faces_arg(faces_b)
+    if face_a.dtype != torch.int32 or face_b.dtype != torch.int32 or face_a.dim() != 1 or face_a.shape != face_b.shape:
+        raise SemigcnLibraryError(f"face_a and face_b must be int32 [N], got {face_a.dtype} {tuple(face_a.shape)} and "
+                                  f"{face_b.dtype} {tuple(face_b.shape)}")
+    face_a, face_b = face_a.contiguous(), face_b.contiguous()
+    out = torch.zeros(2, dtype=torch.float64, device=vs_a.device)
+    if face_a.shape[0]:
+        part = torch.empty(3 * REDUCE_BLOCKS, dtype=torch.float64, device=vs_a.device)
+        with _on_device(vs_a.device):
+            _check(load().sg_normal_agreement(_ptr(vs_a), _ptr(faces_a), _ptr(face_a), _ptr(vs_b), _ptr(faces_b), _ptr(face_b),
+                                              face_a.shape[0], _ptr(part), _ptr(out), _stream(vs_a)), "sg_normal_agreement")
+    return out
 
 
 def mean_edge_length(vs: torch.Tensor, edges: torch.Tensor) -> torch.Tensor:

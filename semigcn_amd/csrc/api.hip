@@ -530,6 +530,71 @@ SG_API int sg_mesh_distance_reduce(const float* q, const float* q_org, float eps
   return mesh_distance_reduce(q, q_org, eps, hole_in, gt_vs, N, hole_out, out, (hipStream_t)stream);
 }
 
+// area-weighted samples and the reductions of the two-sided sampled distance (semigcn_amd/evaluate.py, "Sampling rule"):
+// csrc/mesh_sample.hip
+SG_API int sg_sampler_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, const uint8_t* face_mask_or_null,
+                             void* stream, sg_sampler** out) {
+  SG_REQUIRE(out != nullptr, "sg_sampler_create: null out");
+  *out = nullptr;
+  SG_REQUIRE(F > 0 && V > 0, "sg_sampler_create: need at least one face and one vertex (F = %lld, V = %lld)", (long long)F,
+             (long long)V);
+  SG_REQUIRE(F < ((int64_t)1 << 31) && V < ((int64_t)1 << 31), "sg_sampler_create: sizes must fit int32");
+  SG_REQUIRE(vs && faces, "sg_sampler_create: null pointer");
+  return sampler_create(vs, V, faces, F, face_mask_or_null, (hipStream_t)stream, out);
+}
+
+SG_API int sg_sampler_destroy(sg_sampler* s) {
+  destroy_sampler(s);
+  return SG_OK;
+}
+
+SG_API int sg_sampler_query(const sg_sampler* s, int64_t* info) {
+  SG_REQUIRE(s != nullptr, "sg_sampler_query: null plan");
+  SG_REQUIRE(info != nullptr, "sg_sampler_query: null pointer");
+  sampler_query(s, info);
+  return SG_OK;
+}
+
+SG_API int sg_sampler_export(const sg_sampler* s, uint64_t* w_or_null, uint64_t* cdf_or_null, void* stream) {
+  SG_REQUIRE(s != nullptr, "sg_sampler_export: null plan");
+  return sampler_export(s, w_or_null, cdf_or_null, (hipStream_t)stream);
+}
+
+SG_API int sg_sampler_locate(const sg_sampler* s, const uint64_t* t, int64_t N, int32_t* face, void* stream) {
+  SG_REQUIRE(s != nullptr, "sg_sampler_locate: null plan");
+  SG_REQUIRE(N >= 0 && N < ((int64_t)1 << 31), "sg_sampler_locate: N must be in [0, 2^31), got %lld", (long long)N);
+  if (N == 0) return SG_OK;
+  SG_REQUIRE(t && face, "sg_sampler_locate: null pointer");
+  return sampler_locate(s, t, N, face, (hipStream_t)stream);
+}
+
+SG_API int sg_sampler_draw(const sg_sampler* s, uint64_t seed, uint64_t offset, int64_t N, int order, float* points,
+                           int32_t* face, int32_t* bary_or_null, int64_t* index_or_null, void* stream) {
+  SG_REQUIRE(s != nullptr, "sg_sampler_draw: null plan");
+  SG_REQUIRE(N >= 0 && N < ((int64_t)1 << 31), "sg_sampler_draw: N must be in [0, 2^31), got %lld", (long long)N);
+  SG_REQUIRE(order == SG_SAMPLE_ORDER_FACE || order == SG_SAMPLE_ORDER_DRAW, "sg_sampler_draw: order must be 0 (face) or 1 (draw), got %d",
+             order);
+  if (N == 0) return SG_OK;
+  SG_REQUIRE(points && face, "sg_sampler_draw: null pointer");
+  return sampler_draw(s, seed, offset, N, order, points, face, bary_or_null, index_or_null, (hipStream_t)stream);
+}
+
+SG_API int sg_distance_stats(const float* dist, int64_t N, float tau, double* partial, double* out, void* stream) {
+  SG_REQUIRE(N >= 0 && N < ((int64_t)1 << 31), "sg_distance_stats: N must be in [0, 2^31), got %lld", (long long)N);
+  if (N == 0) return SG_OK;
+  SG_REQUIRE(dist && partial && out, "sg_distance_stats: null pointer");
+  return distance_stats(dist, N, tau, partial, out, (hipStream_t)stream);
+}
+
+SG_API int sg_normal_agreement(const float* vs_a, const int64_t* faces_a, const int32_t* face_a, const float* vs_b,
+                               const int64_t* faces_b, const int32_t* face_b, int64_t N, double* partial, double* out,
+                               void* stream) {
+  SG_REQUIRE(N >= 0 && N < ((int64_t)1 << 31), "sg_normal_agreement: N must be in [0, 2^31), got %lld", (long long)N);
+  if (N == 0) return SG_OK;
+  SG_REQUIRE(vs_a && faces_a && face_a && vs_b && faces_b && face_b && partial && out, "sg_normal_agreement: null pointer");
+  return normal_agreement(vs_a, faces_a, face_a, vs_b, faces_b, face_b, N, partial, out, (hipStream_t)stream);
+}
+
 // preprocess/prepare.py:48-52 (edge_based_scaling) and :110-114 (smooth): csrc/mesh_smooth.hip
 SG_API int64_t sg_edge_length_blocks(int64_t E) { return E >= 0 ? edge_length_blocks(E) : -1; }
 

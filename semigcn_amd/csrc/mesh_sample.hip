@@ -1,0 +1,434 @@
+// Area-weighted surface samples and the reductions of the two-sided sampled distance (semigcn_amd/evaluate.py,
+// "Sampling rule": the specification; tests/sample_oracle.py: its numpy restatement, which this file equals bit for bit).
+//
+// Plan (sg_sampler_create): one pass over the faces checks every vertex id BEFORE the face's vertices are read, keeps a
+// copy of the nine float32 coordinates, computes nn = |e1 x e2|^2 in float64 and the maximum of nn (an integer atomic max
+// on the bit pattern of a non-negative double: exact in any order).  The host takes the exponent of the maximum; a second
+// pass scales nn to below 2^62, takes the exact integer square root as the face's weight, and hipCUB's exclusive sum of the
+// uint64 weights is the cdf.  Everything that chooses is integer, so nothing depends on the order of any reduction.
+//
+// Draw (sg_sampler_draw): one lane per draw k: Philox4x32-10 of (k, seed), t = mulhi64(r, W), a binary search in the cdf
+// (about log2 F dependent reads: latency, not bandwidth), 24-bit barycentrics folded into the triangle, and the point in
+// float64 rounded once.  order "face": the faces of the draws are radix-sorted (stable: ties keep k ascending) and a
+// second launch re-derives each draw from its k, so the barycentrics are never stored in between.
+//
+// Reductions (sg_distance_stats, sg_normal_agreement): block b sums a fixed run of consecutive indices through a tree in
+// LDS, one thread adds the block partials in block order: no floating-point atomics, two runs give the same bits.
+//
+// Built with -ffp-contract=off: nn and the point are DEFINED as plain multiplies and adds.
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <new>
+
+#include "mesh_common.h"
+
+struct sg_sampler {
+  int64_t V = 0, F = 0;
+  int64_t s = 0, n_zero = 0;
+  uint64_t W = 0;
+  sg::DeviceBuf<float> tri;        // [F][9]: A, B, C of every face
+  sg::DeviceBuf<uint64_t> w;       // [F]
+  sg::DeviceBuf<uint64_t> cdf;     // [F + 1]
+};
+
+namespace sg {
+namespace {
+
+constexpr int kOne = 1 << 24;     // the barycentrics are integers out of 2^24
+constexpr int kNoFace = 0x7fffffff;
+
+struct FaceFlags {
+  int bad_index, non_finite;
+  unsigned long long max_bits;    // bit pattern of max nn (nn >= 0: the patterns order as the values do)
+  unsigned long long n_zero;
+};
+
+__device__ __forceinline__ uint64_t wave_max(uint64_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint64_t o = __shfl_down(v, off, 64);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+// nn[f] and the copy of the face's vertices; a face with a bad vertex id reads nothing through it
+__global__ void face_weights_nn(const float* __restrict__ vs, int64_t V, const int64_t* __restrict__ faces, int64_t F,
+                                const uint8_t* __restrict__ mask, float* __restrict__ tri, double* __restrict__ nn_out,
+                                FaceFlags* __restrict__ flags) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  double nn = 0.0;
+  if (f < F) {
+    const int64_t ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
+    if (ia < 0 || ia >= V || ib < 0 || ib >= V || ic < 0 || ic >= V) {
+      flags->bad_index = 1;
+      for (int k = 0; k < 9; ++k) tri[9 * f + k] = 0.f;
+    } else {
+      float p[9];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        p[k] = vs[3 * ia + k];
+        p[3 + k] = vs[3 * ib + k];
+        p[6 + k] = vs[3 * ic + k];
+      }
+#pragma unroll
+      for (int k = 0; k < 9; ++k) tri[9 * f + k] = p[k];
+      const double e1x = (double)p[3] - (double)p[0], e1y = (double)p[4] - (double)p[1], e1z = (double)p[5] - (double)p[2];
+      const double e2x = (double)p[6] - (double)p[0], e2y = (double)p[7] - (double)p[1], e2z = (double)p[8] - (double)p[2];
+      const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+      nn = (nx * nx + ny * ny) + nz * nz;
+      if (!isfinite(nn)) {
+        flags->non_finite = 1;
+        nn = 0.0;
+      }
+      if (mask && mask[f] == 0) nn = 0.0;
+    }
+    nn_out[f] = nn;
+  }
+  const uint64_t m = wave_max((uint64_t)__double_as_longlong(nn));    // lanes past F carry 0
+  if ((threadIdx.x & 63) == 0 && m != 0) atomicMax(&flags->max_bits, (unsigned long long)m);
+}
+
+__device__ __forceinline__ uint64_t isqrt64(uint64_t q) {
+  uint64_t r = (uint64_t)sqrt((double)q);       // q < 2^62: r is within a few units of the root, and r + 1 < 2^32
+  while (r * r > q) --r;
+  while ((r + 1) * (r + 1) <= q) ++r;
+  return r;
+}
+
+__global__ void face_weights(const double* __restrict__ nn, int64_t F, int s, uint64_t* __restrict__ w,
+                             FaceFlags* __restrict__ flags) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool zero = false;
+  if (f < F) {
+    const uint64_t q = (uint64_t)floor(ldexp(nn[f], s));
+    const uint64_t r = isqrt64(q);
+    w[f] = r;
+    zero = r == 0;
+  }
+  const unsigned long long b = __ballot(zero);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(&flags->n_zero, (unsigned long long)__popcll(b));
+}
+
+__global__ void cdf_total(const uint64_t* __restrict__ w, uint64_t* __restrict__ cdf, int64_t F) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) cdf[F] = cdf[F - 1] + w[F - 1];
+}
+
+// the f with cdf[f] <= t < cdf[f + 1]: upper bound over cdf[0 .. F] minus one (cdf[0] = 0 <= t, so it is >= 0)
+__device__ __forceinline__ int locate_face(const uint64_t* __restrict__ cdf, int64_t F, uint64_t t) {
+  int64_t lo = 0, hi = F + 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (cdf[mid] <= t) lo = mid + 1;
+    else hi = mid;
+  }
+  const int64_t f = lo - 1;
+  return (int)(f < F ? f : F - 1);              // t >= W (not a draw: sg_sampler_locate alone) clamps to the last face
+}
+
+__global__ void locate_kernel(const uint64_t* __restrict__ cdf, int64_t F, const uint64_t* __restrict__ t, int64_t N,
+                              int32_t* __restrict__ face) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < N) face[i] = locate_face(cdf, F, t[i]);
+}
+
+struct Philox {
+  uint32_t x[4];
+};
+
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC 2011)
+__device__ __forceinline__ Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return {{c0, c1, c2, c3}};
+}
+
+// what draw k decides besides its face
+struct Draw {
+  uint64_t t;
+  int w0, a, b;
+};
+
+__device__ __forceinline__ Draw draw_k(uint64_t k, uint64_t seed, uint64_t W) {
+  const Philox x = philox4x32_10((uint32_t)k, (uint32_t)(k >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const uint64_t r = (uint64_t)x.x[1] << 32 | x.x[0];
+  Draw d;
+  d.t = __umul64hi(r, W);
+  int a = (int)(x.x[2] >> 8), b = (int)(x.x[3] >> 8);
+  if (a + b > kOne) {
+    a = kOne - a;
+    b = kOne - b;
+  }
+  d.a = a;
+  d.b = b;
+  d.w0 = kOne - a - b;
+  return d;
+}
+
+__device__ __forceinline__ void emit(const float* __restrict__ tri, int f, const Draw& d, uint64_t k, int64_t j,
+                                     float* __restrict__ points, int32_t* __restrict__ face, int32_t* __restrict__ bary,
+                                     int64_t* __restrict__ index) {
+  const float* p = tri + 9 * (int64_t)f;
+  const double w0 = (double)d.w0, a = (double)d.a, b = (double)d.b;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    points[3 * j + c] = (float)(((w0 * (double)p[c] + a * (double)p[3 + c]) + b * (double)p[6 + c]) * 0x1p-24);
+  face[j] = f;
+  if (bary) {
+    bary[3 * j] = d.w0;
+    bary[3 * j + 1] = d.a;
+    bary[3 * j + 2] = d.b;
+  }
+  if (index) index[j] = (int64_t)k;
+}
+
+// order "draw": draw offset + i goes to row i
+__global__ void draw_rows(const float* __restrict__ tri, const uint64_t* __restrict__ cdf, int64_t F, uint64_t W,
+                          uint64_t seed, uint64_t offset, int64_t N, float* __restrict__ points, int32_t* __restrict__ face,
+                          int32_t* __restrict__ bary, int64_t* __restrict__ index) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const uint64_t k = offset + (uint64_t)i;
+  const Draw d = draw_k(k, seed, W);
+  emit(tri, locate_face(cdf, F, d.t), d, k, i, points, face, bary, index);
+}
+
+// order "face", first launch: the sort's keys (the face) and values (i)
+__global__ void draw_faces(const uint64_t* __restrict__ cdf, int64_t F, uint64_t W, uint64_t seed, uint64_t offset, int64_t N,
+                           uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  keys[i] = (uint32_t)locate_face(cdf, F, draw_k(offset + (uint64_t)i, seed, W).t);
+  vals[i] = (uint32_t)i;
+}
+
+// order "face", second launch: row j is the draw whose (face, i) came out j-th
+__global__ void draw_sorted(const float* __restrict__ tri, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                            uint64_t W, uint64_t seed, uint64_t offset, int64_t N, float* __restrict__ points,
+                            int32_t* __restrict__ face, int32_t* __restrict__ bary, int64_t* __restrict__ index) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= N) return;
+  const uint64_t k = offset + (uint64_t)vals[j];
+  emit(tri, (int)keys[j], draw_k(k, seed, W), k, j, points, face, bary, index);
+}
+
+// ---- reductions: K values per index, block partials in index order ----
+
+// rows of the run of block b: [b * chunk, (b + 1) * chunk), chunk a multiple of kThreads
+inline int64_t chunk_for(int64_t N, int nb) {
+  const int64_t c = (N + nb - 1) / nb;
+  return (c + kThreads - 1) / kThreads * kThreads;
+}
+
+inline int blocks_of(int64_t N) { return N == 0 ? 1 : (int)(blocks_for(N) < (unsigned)SG_REDUCE_BLOCKS ? blocks_for(N) : SG_REDUCE_BLOCKS); }
+
+// v[0] is a maximum, v[1 .. K) are sums; thread 0 of the block writes part[K * block + k]
+template <int K>
+__device__ __forceinline__ void block_reduce(double (&v)[K], double* __restrict__ part) {
+  __shared__ double s[K][kThreads];
+#pragma unroll
+  for (int k = 0; k < K; ++k) s[k][threadIdx.x] = v[k];
+  __syncthreads();
+  for (int w = kThreads / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      s[0][threadIdx.x] = fmax(s[0][threadIdx.x], s[0][threadIdx.x + w]);
+#pragma unroll
+      for (int k = 1; k < K; ++k) s[k][threadIdx.x] += s[k][threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < K) part[K * blockIdx.x + threadIdx.x] = s[threadIdx.x][0];
+}
+
+template <int K>
+__global__ void reduce_finish(const double* __restrict__ part, int nb, double* __restrict__ out, int first_out) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double v[K];
+  for (int k = 0; k < K; ++k) v[k] = 0.0;
+  for (int b = 0; b < nb; ++b) {
+    v[0] = fmax(v[0], part[K * b]);
+    for (int k = 1; k < K; ++k) v[k] += part[K * b + k];
+  }
+  for (int k = first_out; k < K; ++k) out[k - first_out] = v[k];
+}
+
+// (max |d|, sum |d|, sum d^2, count |d| <= tau, rows skipped because d is infinite)
+__global__ void stats_partial(const float* __restrict__ dist, int64_t N, int64_t chunk, float tau, double* __restrict__ part) {
+  double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = i0 + chunk < N ? i0 + chunk : N;
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += kThreads) {
+    const float d = dist[i];
+    if (isinf(d)) {
+      v[4] += 1.0;
+      continue;
+    }
+    const double a = fabs((double)d);
+    v[0] = fmax(v[0], a);
+    v[1] += a;
+    v[2] += a * a;
+    if (fabsf(d) <= tau) v[3] += 1.0;
+  }
+  block_reduce<5>(v, part);
+}
+
+__device__ __forceinline__ void face_normal(const float* __restrict__ vs, const int64_t* __restrict__ faces, int64_t f,
+                                            double (&n)[3]) {
+  const float* a = vs + 3 * faces[3 * f];
+  const float* b = vs + 3 * faces[3 * f + 1];
+  const float* c = vs + 3 * faces[3 * f + 2];
+  const double e1x = (double)b[0] - (double)a[0], e1y = (double)b[1] - (double)a[1], e1z = (double)b[2] - (double)a[2];
+  const double e2x = (double)c[0] - (double)a[0], e2y = (double)c[1] - (double)a[1], e2z = (double)c[2] - (double)a[2];
+  n[0] = e1y * e2z - e1z * e2y;
+  n[1] = e1z * e2x - e1x * e2z;
+  n[2] = e1x * e2y - e1y * e2x;
+}
+
+// (unused maximum, sum |cos|, count)
+__global__ void normal_partial(const float* __restrict__ vs_a, const int64_t* __restrict__ faces_a, const int32_t* __restrict__ face_a,
+                               const float* __restrict__ vs_b, const int64_t* __restrict__ faces_b, const int32_t* __restrict__ face_b,
+                               int64_t N, int64_t chunk, double* __restrict__ part) {
+  double v[3] = {0.0, 0.0, 0.0};
+  const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = i0 + chunk < N ? i0 + chunk : N;
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += kThreads) {
+    const int fa = face_a[i], fb = face_b[i];
+    if (fa < 0 || fb < 0 || fa == kNoFace || fb == kNoFace) continue;
+    double na[3], nb[3];
+    face_normal(vs_a, faces_a, fa, na);
+    face_normal(vs_b, faces_b, fb, nb);
+    const double nna = (na[0] * na[0] + na[1] * na[1]) + na[2] * na[2];
+    const double nnb = (nb[0] * nb[0] + nb[1] * nb[1]) + nb[2] * nb[2];
+    if (!(nna > 0.0) || !(nnb > 0.0)) continue;
+    const double c = ((na[0] * nb[0] + na[1] * nb[1]) + na[2] * nb[2]) / sqrt(nna * nnb);
+    if (!isfinite(c)) continue;                 // nna nnb under- or overflowed: no angle to speak of
+    v[1] += fabs(c);
+    v[2] += 1.0;
+  }
+  block_reduce<3>(v, part);
+}
+
+}  // namespace
+
+void destroy_sampler(sg_sampler* s) { delete s; }
+
+int sampler_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, const uint8_t* face_mask, hipStream_t stream,
+                   sg_sampler** out) {
+  std::unique_ptr<sg_sampler> s(new (std::nothrow) sg_sampler);
+  SG_REQUIRE(s != nullptr, "sg_sampler_create: out of host memory");
+  s->V = V;
+  s->F = F;
+  SG_HIP_TRY(s->tri.alloc(9 * (size_t)F));
+  SG_HIP_TRY(s->w.alloc(F));
+  SG_HIP_TRY(s->cdf.alloc((size_t)F + 1));
+  DeviceBuf<double> nn;
+  DeviceBuf<FaceFlags> flags;
+  SG_HIP_TRY(nn.alloc(F));
+  SG_HIP_TRY(flags.alloc(1));
+  SG_HIP_TRY(hipMemsetAsync(flags.p, 0, sizeof(FaceFlags), stream));
+  face_weights_nn<<<blocks_for(F), kThreads, 0, stream>>>(vs, V, faces, F, face_mask, s->tri.p, nn.p, flags.p);
+  SG_HIP_TRY(hipGetLastError());
+  FaceFlags h;
+  SG_HIP_TRY(hipMemcpyAsync(&h, flags.p, sizeof(FaceFlags), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipStreamSynchronize(stream));
+  SG_REQUIRE(!h.bad_index, "sg_sampler_create: face refers to a vertex outside [0, %lld)", (long long)V);
+  SG_REQUIRE(!h.non_finite, "sg_sampler_create: a face has a non-finite squared normal (a NaN or infinite vertex, or an overflow)");
+  double m;
+  static_assert(sizeof(m) == sizeof(h.max_bits), "bit pattern of a double");
+  memcpy(&m, &h.max_bits, sizeof(m));
+  if (m == 0.0) {                       // every weight is 0
+    SG_HIP_TRY(hipMemsetAsync(s->w.p, 0, (size_t)F * sizeof(uint64_t), stream));
+    SG_HIP_TRY(hipMemsetAsync(s->cdf.p, 0, ((size_t)F + 1) * sizeof(uint64_t), stream));
+    SG_HIP_TRY(hipStreamSynchronize(stream));
+    s->n_zero = F;
+    *out = s.release();
+    return SG_OK;
+  }
+  int e = 0;
+  (void)frexp(m, &e);                   // m = f 2^e, f in [0.5, 1)
+  s->s = 62 - e;
+  face_weights<<<blocks_for(F), kThreads, 0, stream>>>(nn.p, F, (int)s->s, s->w.p, flags.p);
+  SG_HIP_TRY(hipGetLastError());
+  const int rc = exclusive_sum(s->w.p, s->cdf.p, F, stream);
+  if (rc != SG_OK) return rc;
+  cdf_total<<<1, 64, 0, stream>>>(s->w.p, s->cdf.p, F);
+  SG_HIP_TRY(hipGetLastError());
+  SG_HIP_TRY(hipMemcpyAsync(&s->W, s->cdf.p + F, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipMemcpyAsync(&h, flags.p, sizeof(FaceFlags), hipMemcpyDeviceToHost, stream));
+  SG_HIP_TRY(hipStreamSynchronize(stream));
+  s->n_zero = (int64_t)h.n_zero;
+  *out = s.release();
+  return SG_OK;
+}
+
+void sampler_query(const sg_sampler* s, int64_t* info) {
+  info[0] = (int64_t)s->W;
+  info[1] = s->s;
+  info[2] = s->n_zero;
+  info[3] = s->F;
+}
+
+int sampler_export(const sg_sampler* s, uint64_t* w, uint64_t* cdf, hipStream_t stream) {
+  if (w) SG_HIP_TRY(hipMemcpyAsync(w, s->w.p, (size_t)s->F * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+  if (cdf) SG_HIP_TRY(hipMemcpyAsync(cdf, s->cdf.p, ((size_t)s->F + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+  return SG_OK;
+}
+
+int sampler_locate(const sg_sampler* s, const uint64_t* t, int64_t N, int32_t* face, hipStream_t stream) {
+  locate_kernel<<<blocks_for(N), kThreads, 0, stream>>>(s->cdf.p, s->F, t, N, face);
+  SG_HIP_TRY(hipGetLastError());
+  return SG_OK;
+}
+
+int sampler_draw(const sg_sampler* s, uint64_t seed, uint64_t offset, int64_t N, int order, float* points, int32_t* face,
+                 int32_t* bary, int64_t* index, hipStream_t stream) {
+  SG_REQUIRE(s->W != 0, "sg_sampler_draw: every face has weight 0 (zero area, or masked out): nothing to draw from");
+  if (order == SG_SAMPLE_ORDER_DRAW) {
+    draw_rows<<<blocks_for(N), kThreads, 0, stream>>>(s->tri.p, s->cdf.p, s->F, s->W, seed, offset, N, points, face, bary, index);
+    SG_HIP_TRY(hipGetLastError());
+    return SG_OK;
+  }
+  AsyncBuf<uint32_t> keys_a(stream), keys_b(stream), vals_a(stream), vals_b(stream);
+  AsyncBuf<char> temp(stream);
+  SG_HIP_TRY(keys_a.alloc(N));
+  SG_HIP_TRY(keys_b.alloc(N));
+  SG_HIP_TRY(vals_a.alloc(N));
+  SG_HIP_TRY(vals_b.alloc(N));
+  draw_faces<<<blocks_for(N), kThreads, 0, stream>>>(s->cdf.p, s->F, s->W, seed, offset, N, keys_a.p, vals_a.p);
+  SG_HIP_TRY(hipGetLastError());
+  const int bits = bits_for((uint64_t)s->F, 32);
+  size_t tb = 0;
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_a.p, keys_b.p, vals_a.p, vals_b.p, (int)N, 0, bits, stream));
+  SG_HIP_TRY(temp.alloc(tb));
+  SG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys_a.p, keys_b.p, vals_a.p, vals_b.p, (int)N, 0, bits, stream));
+  draw_sorted<<<blocks_for(N), kThreads, 0, stream>>>(s->tri.p, keys_b.p, vals_b.p, s->W, seed, offset, N, points, face, bary, index);
+  SG_HIP_TRY(hipGetLastError());
+  return SG_OK;
+}
+
+int distance_stats(const float* dist, int64_t N, float tau, double* partial, double* out, hipStream_t stream) {
+  const int nb = blocks_of(N);
+  stats_partial<<<nb, kThreads, 0, stream>>>(dist, N, chunk_for(N, nb), tau, partial);
+  reduce_finish<5><<<1, 64, 0, stream>>>(partial, nb, out, 0);
+  SG_HIP_TRY(hipGetLastError());
+  return SG_OK;
+}
+
+int normal_agreement(const float* vs_a, const int64_t* faces_a, const int32_t* face_a, const float* vs_b, const int64_t* faces_b,
+                     const int32_t* face_b, int64_t N, double* partial, double* out, hipStream_t stream) {
+  const int nb = blocks_of(N);
+  normal_partial<<<nb, kThreads, 0, stream>>>(vs_a, faces_a, face_a, vs_b, faces_b, face_b, N, chunk_for(N, nb), partial);
+  reduce_finish<3><<<1, 64, 0, stream>>>(partial, nb, out, 1);
+  SG_HIP_TRY(hipGetLastError());
+  return SG_OK;
+}
+
+}  // namespace sg

@@ -352,6 +352,18 @@ int surface_query(const sg_surface* s, const float* pts, int64_t N, int signed_d
                   float* closest, hipStream_t stream);
 int mesh_distance_reduce(const float* q, const float* q_org, float eps, const uint8_t* hole_in, const float* gt_vs,
                          int64_t N, uint8_t* hole_out, double* out, hipStream_t stream);
+// csrc/mesh_sample.hip
+int sampler_create(const float* vs, int64_t V, const int64_t* faces, int64_t F, const uint8_t* face_mask, hipStream_t stream,
+                   sg_sampler** out);
+void destroy_sampler(sg_sampler* s);
+void sampler_query(const sg_sampler* s, int64_t* info);
+int sampler_export(const sg_sampler* s, uint64_t* w, uint64_t* cdf, hipStream_t stream);
+int sampler_locate(const sg_sampler* s, const uint64_t* t, int64_t N, int32_t* face, hipStream_t stream);
+int sampler_draw(const sg_sampler* s, uint64_t seed, uint64_t offset, int64_t N, int order, float* points, int32_t* face,
+                 int32_t* bary, int64_t* index, hipStream_t stream);
+int distance_stats(const float* dist, int64_t N, float tau, double* partial, double* out, hipStream_t stream);
+int normal_agreement(const float* vs_a, const int64_t* faces_a, const int32_t* face_a, const float* vs_b, const int64_t* faces_b,
+                     const int32_t* face_b, int64_t N, double* partial, double* out, hipStream_t stream);
 
 int launch_mesh_loss_bwd_corners(const float* pos, const int64_t* faces, const float* tfn, const float* fkeep, const float* g,
                                  int64_t F, float* corner, hipStream_t stream);
