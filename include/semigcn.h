@@ -591,6 +591,44 @@ SG_API int sg_fair_solve(sg_fair* s, const float* in, float* out, double tol, in
                          void* stream, int64_t* iterations, double* relative_residual, int* converged);
 
 /* ------------------------------------------------------------------------- *
+ * Vertex updating -- replaces Models.vertex_updating (util/models.py:239-252),
+ * the second half of the two-stage denoiser whose first half is sg_bnf_filter:
+ * move the vertices so that the faces meet given (filtered) normals.  The rule
+ * is specified in semigcn_amd/denoise.py, "The rule"; one step, in float32 with
+ * plain multiplies and adds, from the positions p of the step before:
+ *     c_f  = ((p_a + p_b) + p_c) / 3.0f            a, b, c = faces[f]
+ *     s    = 0; over the faces f_1 < ... < f_k that name vertex i, in that order:
+ *            d = c_f - p_i;  t = (n_x d_x + n_y d_y) + n_z d_z;  s = s + t n_f
+ *     p_i' = p_i + s / float(k)
+ *
+ * sg_vupdate_create: the vertex -> face lists in ascending face order, from
+ *   faces int64 [F,3] (device) over V vertices.  A face index outside [0, V) or
+ *   a face with a repeated vertex gives SG_ERR_INVALID.  F == 0 makes a plan
+ *   without touching a device (V == 0 with F > 0 is refused without one).
+ *   Synchronises the stream.
+ * sg_vupdate_query: info[4] (host) = V, F, the largest number of faces at one
+ *   vertex, the number of vertices without a face.
+ * sg_vupdate_run: `steps` steps from pos float32 [V,3] with normals float32 [F,3]
+ *   (used as given: not normalised, non-finite values propagate) to out float32
+ *   [V,3], which may not overlap pos.  A vertex without a face, or with
+ *   movable_or_null[i] == 0 (V bytes), keeps its position bit for bit and still
+ *   feeds the centroids.  steps == 0 copies.  One launch packs the positions and
+ *   the normals into the plan's 16-byte records, then two launches per step (the
+ *   centroids, the vertices), ping-ponging between the plan's two buffers; the
+ *   last step writes out.  No atomics, no grid barrier, no host synchronisation;
+ *   bit-reproducible, and a steps followed by b steps equal a + b steps bit for
+ *   bit.  The buffers belong to the plan: one run at a time per plan.  A null
+ *   pointer, steps < 0 or out == pos gives SG_ERR_INVALID before any device is
+ *   touched.
+ * ------------------------------------------------------------------------- */
+typedef struct sg_vupdate sg_vupdate;
+SG_API int sg_vupdate_create(const int64_t* faces, int64_t F, int64_t V, void* stream, sg_vupdate** out);
+SG_API int sg_vupdate_destroy(sg_vupdate* s);
+SG_API int sg_vupdate_query(const sg_vupdate* s, int64_t* info);
+SG_API int sg_vupdate_run(sg_vupdate* s, const float* pos, const float* normals, const uint8_t* movable_or_null, int steps,
+                          float* out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Connected components -- replaces the first step of MeshFix.repair()
  * (preprocess/prepare.py:28-33): label the components of a triangle list, keep
  * some of them, compact vertices and faces.  The definitions (connectivities,

@@ -229,6 +229,10 @@ _SIGNATURES = {
     "sg_fair_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_fair_solve": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_double, c_int64, c_int64, c_void_p, POINTER(c_int64),
                               POINTER(ctypes.c_double), POINTER(c_int)]),
+    "sg_vupdate_create": (c_int, [c_void_p, c_int64, c_int64, c_void_p, POINTER(c_void_p)]),
+    "sg_vupdate_destroy": (c_int, [c_void_p]),
+    "sg_vupdate_query": (c_int, [c_void_p, POINTER(c_int64)]),
+    "sg_vupdate_run": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "sg_parts_create": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, POINTER(c_void_p)]),
     "sg_parts_destroy": (c_int, [c_void_p]),
     "sg_parts_query": (c_int, [c_void_p, POINTER(c_int64)]),
@@ -1241,11 +1245,17 @@ def _i64c(t: torch.Tensor, name: str, rows: int) -> torch.Tensor:
     return t
 
 
+def bnf_scratch(F: int, device) -> torch.Tensor:
+    """The work space of ``bnf_filter`` for a mesh of ``F`` faces."""
+    return torch.empty((_sizes("sg_bnf_scratch_bytes", F) // 4,), dtype=torch.float32, device=device)
+
+
 def bnf_filter(pos: torch.Tensor, faces: torch.Tensor, f2f: torch.Tensor, loop: int = 5, sigma_s: float = 0.3,
-               start_fn: Optional[torch.Tensor] = None, with_partials: bool = False):
+               start_fn: Optional[torch.Tensor] = None, with_partials: bool = False, scratch: Optional[torch.Tensor] = None):
     """(fn [F,3], n_filtered [F,3], block partials of sum_f |n_filtered - fn|_1 or None): ``loop`` rounds of the bilateral
     face-normal filter over the face ring ``f2f`` (util/models.py:209-237, util/loss.py:197-232), started from ``start_fn``
-    (None: the face normals of ``pos``).  3 + loop launches on the current stream, no host synchronisation."""
+    (None: the face normals of ``pos``).  3 + loop launches on the current stream, no host synchronisation.  ``scratch``:
+    ``bnf_scratch(F, device)`` of a caller that filters the same mesh again and again (None: allocated here)."""
     F = faces.shape[0]
     _f32c(pos, "pos"), _i64c(faces, "faces", F), _i64c(f2f, "f2f", F)
     if pos.dim() != 2 or pos.shape[1] != 3:
@@ -1255,7 +1265,10 @@ def bnf_filter(pos: torch.Tensor, faces: torch.Tensor, f2f: torch.Tensor, loop: 
     fn = torch.empty((F, 3), dtype=torch.float32, device=pos.device)
     nf = torch.empty((F, 3), dtype=torch.float32, device=pos.device)
     part = torch.empty((_sizes("sg_bnf_blocks", F),), dtype=torch.float32, device=pos.device) if with_partials else None
-    scratch = torch.empty((_sizes("sg_bnf_scratch_bytes", F) // 4,), dtype=torch.float32, device=pos.device)
+    if scratch is None:
+        scratch = bnf_scratch(F, pos.device)
+    elif scratch.dtype != torch.float32 or scratch.device != pos.device or scratch.numel() * 4 < _sizes("sg_bnf_scratch_bytes", F):
+        raise SemigcnLibraryError(f"scratch must be bnf_scratch({F}, {pos.device})")
     with _on_device(pos.device):
         _check(load().sg_bnf_filter(_ptr(pos), _ptr(faces), _ptr(f2f), pos.shape[0], F, int(loop), float(sigma_s), _ptr(start_fn),
                                     _ptr(fn), _ptr(nf), _ptr(part), _ptr(scratch), _stream(pos)), "sg_bnf_filter")
@@ -1791,6 +1804,52 @@ class FairPlan(_OwnedHandle):
                                         byref(it), res, byref(ok)), "sg_fair_solve")
         return out, {"iterations": int(it.value), "relative_residual": [float(v) for v in res], "converged": bool(ok.value),
                      "n_free": self.num_free}
+
+
+class VertexUpdatePlan(_OwnedHandle):
+    """Owns one sg_vupdate (csrc/mesh_denoise.hip): the vertex -> face lists of a triangle list in ascending face order and
+    the buffers the steps of the vertex update ping-pong between (the rule is specified in semigcn_amd/denoise.py).
+    ``max_valence`` is the largest number of faces at one vertex, ``num_unused`` the number of vertices without a face.
+    One ``run`` at a time per plan."""
+
+    _destroy = "sg_vupdate_destroy"
+    _query_fn, _query_len = "sg_vupdate_query", 4
+
+    def __init__(self, faces: torch.Tensor, num_vertices: int):
+        _require_device(faces, "faces")
+        faces = _faces_arg(faces)
+        self.device, self.num_vertices, self.num_faces = faces.device, int(num_vertices), faces.shape[0]
+        self._create("sg_vupdate_create", faces.device, _ptr(faces), faces.shape[0], self.num_vertices, _stream(faces))
+        self.max_valence, self.num_unused = (int(v) for v in self._query()[2:4])
+
+    def run(self, pos: torch.Tensor, normals: torch.Tensor, movable: Optional[torch.Tensor] = None,
+            steps: int = 10) -> torch.Tensor:
+        """float32 [V, 3]: ``steps`` steps from ``pos`` towards the face normals ``normals`` float32 [F, 3]; ``movable``
+        bool [V] (False = the vertex stays)."""
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError(f"steps must be >= 0, got {steps}")
+        _require_device(pos, "pos")
+        _require_device(normals, "normals")
+        _vs_arg(pos, self)
+        if normals.dtype != torch.float32 or tuple(normals.shape) != (self.num_faces, 3) or normals.device != self.device:
+            raise SemigcnLibraryError(f"normals must be float32 [{self.num_faces}, 3] on {self.device}, got {normals.dtype} "
+                                      f"{tuple(normals.shape)} on {normals.device}")
+        self._open()
+        if movable is not None:
+            _require_device(movable, "movable")
+            if movable.numel() != self.num_vertices or movable.device != self.device:
+                raise SemigcnLibraryError(f"movable must hold {self.num_vertices} entries on {self.device}, got "
+                                          f"{tuple(movable.shape)} on {movable.device}")
+            movable = (movable.reshape(-1) != 0).contiguous()          # bool: one byte per vertex, 0 / 1
+        pos, normals = pos.detach().contiguous(), normals.detach().contiguous()
+        if self.num_vertices == 0 or self.num_faces == 0:              # an empty array has no address to hand over
+            return pos.clone()
+        out = torch.empty_like(pos)
+        with _on_device(pos.device):
+            _check(load().sg_vupdate_run(self._h, _ptr(pos), _ptr(normals), _ptr(movable), steps, _ptr(out), _stream(pos)),
+                   "sg_vupdate_run")
+        return out
 
 
 class PartsPlan(_OwnedHandle):

@@ -707,6 +707,36 @@ SG_API int sg_fair_solve(sg_fair* s, const float* in, float* out, double tol, in
   return fair_solve(s, in, out, tol, max_iter, check_every, (hipStream_t)stream, iterations, relative_residual, converged);
 }
 
+// vertex updating, the second half of the two-stage denoiser (semigcn_amd/denoise.py, "The rule"): csrc/mesh_denoise.hip
+SG_API int sg_vupdate_create(const int64_t* faces, int64_t F, int64_t V, void* stream, sg_vupdate** out) {
+  SG_REQUIRE(out != nullptr, "sg_vupdate_create: null out");
+  *out = nullptr;
+  SG_REQUIRE(F >= 0 && V >= 0, "sg_vupdate_create: negative size (F = %lld, V = %lld)", (long long)F, (long long)V);
+  SG_REQUIRE(F == 0 || faces, "sg_vupdate_create: null pointer");
+  return vupdate_create(faces, F, V, (hipStream_t)stream, out);
+}
+
+SG_API int sg_vupdate_destroy(sg_vupdate* s) {
+  destroy_vupdate(s);
+  return SG_OK;
+}
+
+SG_API int sg_vupdate_query(const sg_vupdate* s, int64_t* info) {
+  SG_REQUIRE(s != nullptr, "sg_vupdate_query: null plan");
+  SG_REQUIRE(info != nullptr, "sg_vupdate_query: null pointer");
+  vupdate_query(s, info);
+  return SG_OK;
+}
+
+SG_API int sg_vupdate_run(sg_vupdate* s, const float* pos, const float* normals, const uint8_t* movable_or_null, int steps,
+                          float* out, void* stream) {
+  SG_REQUIRE(steps >= 0, "sg_vupdate_run: negative steps %d", steps);
+  SG_REQUIRE(s != nullptr, "sg_vupdate_run: null plan");
+  SG_REQUIRE(pos && normals && out, "sg_vupdate_run: null pointer");
+  SG_REQUIRE(pos != out, "sg_vupdate_run: out is pos");
+  return vupdate_run(s, pos, normals, movable_or_null, steps, out, (hipStream_t)stream);
+}
+
 // the component selection of MeshFix.repair() (preprocess/prepare.py:28-33): csrc/mesh_parts.hip
 SG_API int sg_parts_create(const int64_t* faces, int64_t F, int64_t V, int connectivity, void* stream, sg_parts** out) {
   SG_REQUIRE(out != nullptr, "sg_parts_create: null out");

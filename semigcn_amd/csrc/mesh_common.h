@@ -1,9 +1,9 @@
-// What the mesh stages (mesh_prep, mesh_smooth, mesh_fill, mesh_parts, mesh_manifold, mesh_remesh, mesh_dist, mesh_isect, mesh_fair, mesh_sample) share on the host
+// What the mesh stages (mesh_prep, mesh_smooth, mesh_fill, mesh_parts, mesh_manifold, mesh_remesh, mesh_dist, mesh_isect, mesh_fair, mesh_sample, mesh_denoise) share on the host
 // side: typed device buffers that own their memory, the launch geometry, the bit count behind the radix-sort ranges, the
 // exclusive scan, and the kernels and the one device helper that were literal copies.  The rule that goes with it: device
 // memory of a plan or of a call is a typed member or local that frees itself -- never a raw pointer on a hand-kept free list.
-// No floating-point code belongs here: mesh_isect.hip, mesh_remesh.hip, mesh_manifold.hip, mesh_fair.hip and mesh_sample.hip
-// are built with -ffp-contract=off, the others not.
+// No floating-point code belongs here: mesh_isect.hip, mesh_remesh.hip, mesh_manifold.hip, mesh_fair.hip, mesh_sample.hip and
+// mesh_denoise.hip are built with -ffp-contract=off, the others not.
 #pragma once
 #include <hipcub/hipcub.hpp>
 
@@ -102,7 +102,8 @@ __global__ void widen32(const int32_t* __restrict__ in, int64_t n, T* __restrict
   if (i < n) out[i] = in[i];
 }
 
-// The neighbour lists of mesh_smooth.hip and mesh_fair.hip start here (templates for the same reason).  Face-edge
+// The neighbour lists of mesh_smooth.hip and mesh_fair.hip start here (templates for the same reason); row_starts also bounds
+// the vertex -> face lists of mesh_denoise.hip.  Face-edge
 // h = 3 f + i joins a = faces[f][i] and b = faces[f][(i+1)%3]; it puts b on a's list and a on b's: keys (a << 32 | b) and
 // (b << 32 | a).  flags[0]: vertex id out of range; flags[1]: degenerate face (repeated vertex).
 template <class Key>

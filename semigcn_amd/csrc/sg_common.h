@@ -402,6 +402,12 @@ int fair_diagonal(const sg_fair* s, double* out, hipStream_t stream);
 int fair_apply(sg_fair* s, const double* p, double* q, hipStream_t stream);
 int fair_solve(sg_fair* s, const float* in, float* out, double tol, int64_t max_iter, int64_t check_every, hipStream_t stream,
                int64_t* iterations, double* relres, int* converged);
+// mesh_denoise.hip
+int vupdate_create(const int64_t* faces, int64_t F, int64_t V, hipStream_t stream, sg_vupdate** out);
+void destroy_vupdate(sg_vupdate* s);
+void vupdate_query(const sg_vupdate* s, int64_t* info);
+int vupdate_run(sg_vupdate* s, const float* pos, const float* normals, const uint8_t* movable, int steps, float* out,
+                hipStream_t stream);
 // mesh_parts.hip
 int parts_create(const int64_t* faces, int64_t F, int64_t V, int connectivity, hipStream_t stream, sg_parts** out);
 void destroy_parts(sg_parts* s);

@@ -1,9 +1,9 @@
 """What the mesh stages share in Python: the sibling of csrc/mesh_common.h.
 
-``evaluate``, ``prepare``, ``holes``, ``manifold``, ``components``, ``repair``, ``remesh`` and ``simplify`` take their inputs, read and write their OBJ
+``evaluate``, ``prepare``, ``holes``, ``manifold``, ``components``, ``repair``, ``remesh``, ``simplify`` and ``denoise`` take their inputs, read and write their OBJ
 files and time their stages through this module, and through nothing of each other's that starts with an underscore.
 
-The lifetime rule of the objects those stages build (``capi.SmoothPlan`` / ``FillPlan`` / ``FairPlan`` / ``PartsPlan`` / ``ManifoldPlan`` / ``RemeshPlan`` / ``SamplerPlan``,
+The lifetime rule of the objects those stages build (``capi.SmoothPlan`` / ``FillPlan`` / ``FairPlan`` / ``PartsPlan`` / ``ManifoldPlan`` / ``RemeshPlan`` / ``SamplerPlan`` / ``VertexUpdatePlan``,
 ``evaluate.Surface``): one made inside a function lives in a ``with``.  Leaving the block waits for the device's current
 stream and then closes the object, in that order, with or without an exception -- the object's buffers are freed with it,
 and a kernel launched inside the block may still read them.
