@@ -914,7 +914,7 @@ SG_API int sg_mesh_loss_cad_bwd_det(const float* pos, const int64_t* faces, cons
  * moments != NULL is served by the 128-row kernel; sg_gemm_nt_takes_big_tile tells which kernel a moments-free call gets.
  * ------------------------------------------------------------------------- */
 SG_API int sg_gemm_nt_takes_big_tile(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc);
-SG_API int64_t sg_gemm_tile_rows(int64_t N);             /* R for an N-column product (128, or 64 for wide outputs) */
+SG_API int64_t sg_gemm_tile_rows(int64_t N);             /* R for an N-column product (128) */
 SG_API int64_t sg_gemm_row_tiles(int64_t M, int64_t N);  /* ceil(M / R) */
 SG_API int sg_gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb, const float* bias, void* C, int64_t ldc,
                       int64_t M, int64_t N, int64_t K, int dtype, float* moments, void* stream);
@@ -1225,14 +1225,12 @@ enum sg_tune_knob {
                              between the staging phases instead of wavefront-local ones, bit 4: 64-bit gather addressing
                              even where 32-bit offsets would do, bit 5: fixed-size gather batches also where the
                              row length is wave-uniform, bit 6: nontemporal epilogue loads / stores (no effect measured),
-                             bit 7: the experimental unpipelined LDS-tile kernel (set it when the graph is created AND when it is
-                             applied; measured slower), bit 8: 4-channel bf16 rows on the one-thread-per-element kernel instead of the
+                             bit 8: 4-channel bf16 rows on the one-thread-per-element kernel instead of the
                              one-thread-per-row kernel, bit 11: NO tiled matrix-core kernel (spmm_ring) for bf16 rows of 128 / 256
                              channels (at graph creation: no tile records are built), bit 12: spmm_ring stores straight from the
-                             MFMA layout instead of full rows through LDS, bit 13: NO tiled kernel for float32 rows (A/B switches) */
-  SG_TUNE_UNROLL = 2,     /* gathers a lane group issues back to back in the aggregation kernel: 8, 6 or 4
-                             (fewer = fewer VGPRs = more resident wavefronts); 0 = the shipped choice per shape */
-  SG_TUNE_SLAB = 3,       /* channels per column slab (one sweep of all rows per slab); 0 = off */
+                             MFMA layout instead of full rows through LDS, bit 13: NO tiled kernel for float32 rows (A/B switches);
+                             any other bit is refused */
+  /* knobs 2 and 3 are retired: sg_tuning_set refuses them */
   SG_TUNE_TILED_MIN_ROW_BYTES = 4, /* shared-gather kernel (each distinct source row of a 4-row mini-tile is
                                      gathered once): default 1024 = fp32 rows of >= 1 KiB where it pays;
                                      negative = force it for every row of at least |value| bytes and both
@@ -1241,9 +1239,8 @@ enum sg_tune_knob {
                                 where the caller expects them): 0 = when the vertex numbering has no locality (>= 25 % of
                                 the edges span more than 4096 ids, V >= 65536), 1 = never, 2 = always */
   SG_TUNE_GEMM_TILE = 5,  /* sg_gemm_nt kernel: 0 = automatic (shipped: 128 x min(N,128) tiles, the persistent 256 x 256 kernel
-                             for the compute-bound products), 1 = 128-row tiles only, 2 = 64 x 256 wherever N > 64 (A/B
-                             switch; measured slower), 3 = the 256 x 256 kernel wherever it takes the shape, 4 = no 128 x 192 tiles for
-                             N = 192 (A/B switch), 5 = 128 x 192 tiles also for N = 384 (A/B switch; measured slower) */
+                             for the compute-bound products), 1 = 128-row tiles only, 3 = the 256 x 256 kernel wherever it takes the shape,
+                             4 = no 128 x 192 tiles for N = 192 (A/B switch); any other value is refused */
   SG_TUNE_BLOCK_PLANES = 7, /* sg_block_*: 1 (default) = narrow layers keep their recurrence buffers as planes
                               (sg_block_planar), 0 = column blocks everywhere (A/B switch) */
   SG_TUNE_F32_ENGINE = 8,  /* dense products on float32 features: 0 (default) = the split-bf16 MFMA kernels (csrc/gemm_split.hip)

@@ -289,33 +289,33 @@ int launch(GemmArgs g, hipStream_t stream) {
 
 inline bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-int g_gemm_tile = 0;   // SG_TUNE_GEMM_TILE: 0 = automatic, 1 = 128-row tiles only, 2 = 64 x 256 tiles wherever N > 64,
-                       // 3 = the 256 x 256 eight-wavefront kernel (gemm_mfma256.hip) wherever it takes the shape
+int g_gemm_tile = 0;   // SG_TUNE_GEMM_TILE: 0 = automatic, 1 = 128-row tiles only, 3 = the 256 x 256 eight-wavefront kernel
+                       // (gemm_mfma256.hip) wherever it takes the shape, 4 = no 128 x 192 tiles (2 and 5 are retired)
 
 // automatic choice: the persistent 256 x 256 kernel serves the compute-bound products (K x N above ~100 K elements: the
 // 256- and 512-channel layers and [V,384] x [384,256]), the 128-row-tile kernel below the HBM-bound ones
 constexpr int64_t kBigMinWeightElems = 90000;
 constexpr int64_t kBigMinRows = 16384;
 
-// 64 x 256 tiles (ONE column tile covers N <= 256, so A is fetched by one workgroup only) were measured SLOWER than
-// 128 x 128 tiles on every wide product (e.g. [V,384]x[384,256]: 0.43 ms against 0.33 ms; profiles/
-// r02_mfma_gemm_bench.json): the column tiles of a row tile already share A through L2 (XCD-contiguous tile order),
-// and the narrower row tile re-streams B twice as often.  Kept behind the knob for A/B runs only.
-bool wide_tile(int64_t N) { return g_gemm_tile == 2 && N > 64; }
 // (measured at V = 1 M, profiles/r04_gemm192_bench.json: N = 192 0.199 -> 0.174 ms at K = 128, 0.143 -> 0.115 at K = 64; N = 384 as
 // two such tiles at two workgroups per CU is SLOWER than three 128-column tiles at three: 0.393 -> 0.442 ms; 4: A/B switch, off)
-bool tile_192(int64_t N) { return g_gemm_tile != 1 && g_gemm_tile != 4 && (N == 192 || (g_gemm_tile == 5 && N == 384)); }
+bool tile_192(int64_t N) { return g_gemm_tile != 1 && g_gemm_tile != 4 && N == 192; }
 
 }  // namespace
 
-int gemm_tile_rows(int64_t N) { return wide_tile(N) ? 64 : 128; }
+// every product of this file runs on 128-row tiles (64 x 256 tiles are retired: DESIGN.md, "Retired variants")
+int gemm_tile_rows(int64_t) { return 128; }
 
 bool gemm_nt_takes_big_tile(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc) {
-  if (g_gemm_tile == 1 || g_gemm_tile == 2 || !gemm_nt_256_supported(M, N, K, lda, ldb, ldc)) return false;
+  if (g_gemm_tile == 1 || !gemm_nt_256_supported(M, N, K, lda, ldb, ldc)) return false;
   return g_gemm_tile == 3 || (K * N > kBigMinWeightElems && M >= kBigMinRows);
 }
 
 int set_gemm_tuning(int value) {
+  if (value != 0 && value != 1 && value != 3 && value != 4) {
+    set_error("sg_tuning_set: SG_TUNE_GEMM_TILE takes 0, 1, 3 or 4, not %d (2 and 5 are retired)", value);
+    return SG_ERR_INVALID;
+  }
   g_gemm_tile = value;
   return SG_OK;
 }
@@ -338,7 +338,6 @@ int launch_gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb, const
     SG_REQUIRE((!pa.on() || (pa.log2 >= 3 && pa.log2 < 31 && pa.stride % 8 == 0)) &&
                (!pc.on() || (pc.log2 >= 3 && pc.log2 < 31 && pc.stride % 8 == 0)),
                "sg_gemm_nt: planes need >= 8 columns each and a plane stride that is a multiple of 8 elements");
-    SG_REQUIRE(!wide_tile(N), "sg_gemm_nt: operands kept as planes run on the 128-row tiles only");
   }
   if (!planes && moments == nullptr && gemm_nt_takes_big_tile(M, N, K, lda, ldb, ldc))
     return launch_gemm_nt_256(A, lda, B, ldb, bias, C, ldc, M, N, K, stream);
@@ -352,7 +351,6 @@ int launch_gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb, const
   g.moments = moments;
   g.M = (int)M; g.N = (int)N; g.K = (int)K;
   g.n_col_tiles = g.n_tiles = 0;
-  if (wide_tile(N)) return launch<1, 4, 4, 4>(g, stream);  // 64 x 256, wavefront tile 64 x 64
   // N = 192 (the products around the 64 <-> 128-channel layers: [V,128]x[128,192]): ONE 128 x 192 tile per row tile, wavefront
   // tile 64 x 96 -- no half-empty second column tile, A staged once
   if (tile_192(N) && !moments) return launch<2, 2, 4, 6>(g, stream);
@@ -548,7 +546,7 @@ __global__ __launch_bounds__(1024) void tn_reduce(const float* __restrict__ W, i
 // automatic choice for the weight gradient: the 256 x 256 ring (gemm_mfma256.hip) serves the compute-bound products
 // (N, Kp multiples of 256, N x Kp above ~100 K elements), the 128 x 128 kernel below the rest
 bool gemm_tn_takes_big_tile(int64_t M, int64_t N, int64_t Kp, int64_t lda, int64_t ldb) {
-  if (g_gemm_tile == 1 || g_gemm_tile == 2 || !gemm_tn_256_supported(M, N, Kp, lda, ldb)) return false;
+  if (g_gemm_tile == 1 || !gemm_tn_256_supported(M, N, Kp, lda, ldb)) return false;
   return g_gemm_tile == 3 || (N * Kp > kBigMinWeightElems && M >= kBigMinRows);
 }
 

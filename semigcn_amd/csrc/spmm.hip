@@ -38,8 +38,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 enum : int { kFlagXcdMap = 1, kFlagNoTiles = 2, kFlagNoPackedScale = 4, kFlagBlockBarrier = 8, kFlagWideAddr = 16, kFlagNoExact = 32,
-             kFlagStreamEpilogue = 64, kFlagLdsTiles = 128, kFlagNoQuad = 256, kFlagThreadRows = 512, kFlagNoRing = 2048, kFlagRingDirectStores = 4096,
-             kFlagNoRingF32 = 8192 };
+             kFlagStreamEpilogue = 64, kFlagNoQuad = 256, kFlagNoRing = 2048, kFlagRingDirectStores = 4096, kFlagNoRingF32 = 8192 };
+// every bit sg_tuning_set accepts (bits 7 and 9 selected kernels that are retired: DESIGN.md, "Retired variants")
+constexpr int kFlagsKept = kFlagXcdMap | kFlagNoTiles | kFlagNoPackedScale | kFlagBlockBarrier | kFlagWideAddr | kFlagNoExact |
+                           kFlagStreamEpilogue | kFlagNoQuad | kFlagNoRing | kFlagRingDirectStores | kFlagNoRingF32;
 
 // Every wavefront stages ITS OWN chunk in its own LDS slice, so nothing crosses wavefronts: LDS operations of
 // one wavefront complete in issue order, and a compiler-level wave barrier keeps the reads behind the writes.
@@ -585,177 +587,17 @@ __global__ __launch_bounds__(kBlock) void spmm_shared(const SpmmArgs a, const in
 struct Tuning {
   int chunk_rows = 0;             // 0 = automatic
   int flags = kFlagXcdMap;        // kFlag* bits
-  int unroll = 0;                 // 0 = default per shape
-  int slab = 0;                   // channels per column slab; 0 = whole rows
   int tiled_min_row_bytes = 1024; // shared-gather kernel: see launch_typed_one; 0 = never (and build no mini-tiles)
 };
 Tuning g_tuning;
 
 // ---------------------------------------------------------------------------------------------
-// LDS-tile variant (north_star: "neighbour feature tiles staged in LDS") -- EXPERIMENTAL, opt-in (SG_TUNE_FLAGS bit 7 when
-// the graph is created and when it is applied), measured SLOWER than spmm_rows: one workgroup (2 wavefronts) owns a tile
-// of kLdsRows = 16 consecutive rows.  The tile's DISTINCT source rows (~36 for 16 rows in Morton order, 96 edges) are
-// brought into LDS ONCE with global_load_lds_dwordx4 (LDS-DMA: no VGPR round trip), then every output row sums its
-// neighbours out of LDS in CSR order with the same fma chain as spmm_rows -- bit-identical results, and the L2 -> L1
-// request stream drops from 6 rows per output row to ~2.2.  ~25 KB of LDS per workgroup at 512-B rows -> 6 tiles in
-// flight per CU.  Measured on the Morton-ordered 1 M-vertex mesh: bf16 C=256 + epilogue 0.56 ms
-// against 0.36 ms, fp32 C=256 1.48 against 0.70 -- every tile pays its metadata chain, the DMA round trip and the
-// reduction one after the other, and 12 wavefronts per CU do not cover that; kept as the measured answer to "why not LDS
-// tiles", and as a working LDS-DMA gather to build a pipelined version on.
-// ---------------------------------------------------------------------------------------------
-constexpr int kLdsBlock = 128;
-
-template <typename T, int G, int NEPI>
-__global__ __launch_bounds__(kLdsBlock) void spmm_lds(const SpmmArgs a, const int nblocks, const int flags) {
-  using V = Vt<T>;
-  constexpr int VEC = V::VEC;
-  constexpr int RPW = 64 / G;                      // rows (and DMA slots) one wavefront instruction covers
-  constexpr int ROWB = G * 16;                     // bytes of one feature row
-  using raw_t = typename V::raw;
-  using elem_t = typename V::elem;
-
-  __shared__ __attribute__((aligned(16))) uint8_t s_data[kLdsSlots * ROWB];
-  __shared__ int2 s_u[kLdsSlots];
-  __shared__ int32_t s_rp[kLdsRows + 1];
-  __shared__ float s_sd[kLdsRows];
-  __shared__ int32_t s_row[kLdsRows];
-  __shared__ uint8_t s_el[kLdsEdges];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int t = (flags & kFlagXcdMap) ? xcd_contiguous(blockIdx.x, nblocks) : (int)blockIdx.x;
-  const int r0 = t * kLdsRows;
-  int nrows = a.n_rows - r0;
-  nrows = nrows > kLdsRows ? kLdsRows : nrows;
-
-  // ---- tile metadata: row pointers / scales / row ids, then the distinct-source list and every edge's slot ----
-  if (tid <= nrows) s_rp[tid] = a.rowptr[r0 + tid];
-  if (tid < nrows) {
-    s_sd[tid] = a.scale_dst ? a.scale_dst[r0 + tid] : 1.0f;
-    s_row[tid] = a.row_id ? a.row_id[r0 + tid] : r0 + tid;
-  }
-  const int ub = a.lt_uptr[t];
-  const int nu = a.lt_uptr[t + 1] - ub;
-  if (tid < nu) s_u[tid] = a.lt_uniq_w[ub + tid];
-  __syncthreads();
-  const int e0 = s_rp[0], ne = s_rp[nrows] - e0;
-  // a tile without a source list although it has edges did not fit the LDS budget (Morton seam, hub vertex, duplicate
-  // edges): its rows gather from global memory, edge by edge, in the same order
-  const bool in_lds = nu > 0;
-  if (in_lds)
-    for (int k = tid; k < ne; k += kLdsBlock) s_el[k] = a.lt_eloc[e0 + k];
-
-  // ---- LDS-DMA of the source rows: one wavefront instruction = RPW slots of ROWB bytes, 16 B per lane ----
-  const elem_t* __restrict__ X = (const elem_t*)a.X;
-  const int g = lane / G, gl = lane % G;
-  const int n_inst = (nu + RPW - 1) / RPW;
-  for (int i = wave; i < n_inst; i += kLdsBlock / 64) {
-    int slot = i * RPW + g;
-    slot = slot < nu ? slot : nu - 1;               // the tail re-reads the last source row (its LDS slot is unused)
-    const elem_t* src = X + (int64_t)s_u[slot].x * a.ldx + gl * VEC;
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
-                                     (void __attribute__((address_space(3)))*)(s_data + i * (RPW * ROWB)), 16, 0, 0);
-  }
-
-  const elem_t* __restrict__ X0 = (const elem_t*)a.X0;
-  const elem_t* __restrict__ X1 = (const elem_t*)a.X1;
-  elem_t* __restrict__ Y = (elem_t*)a.Y;
-  constexpr int ROWS_PER_IT = RPW * (kLdsBlock / 64);
-  // the epilogue operands of the first row go out together with the DMA
-  raw_t x0v, x1v;
-  {
-    const int lr = wave * RPW + g;
-    const int row = s_row[lr < nrows ? lr : 0];
-    if (NEPI >= 1) x0v = *(const raw_t*)(X0 + (int64_t)row * a.ldx0 + gl * VEC);
-    if (NEPI >= 2) x1v = *(const raw_t*)(X1 + (int64_t)row * a.ldx1 + gl * VEC);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int it = 0; it * ROWS_PER_IT < nrows; ++it) {
-    const int lr = it * ROWS_PER_IT + wave * RPW + g;
-    const bool rvalid = lr < nrows;
-    const int lrc = rvalid ? lr : 0;
-    const int row = s_row[lrc];
-    const int ks = s_rp[lrc] - e0;
-    const int ke = rvalid ? s_rp[lrc + 1] - e0 : ks;
-    raw_t nx0, nx1;                                 // next row's epilogue operands, in flight under this row's sums
-    {
-      const int nl = lr + ROWS_PER_IT;
-      const int nrow = s_row[nl < nrows ? nl : 0];
-      if (NEPI >= 1) nx0 = *(const raw_t*)(X0 + (int64_t)nrow * a.ldx0 + gl * VEC);
-      if (NEPI >= 2) nx1 = *(const raw_t*)(X1 + (int64_t)nrow * a.ldx1 + gl * VEC);
-    }
-    float acc[VEC];
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) acc[c] = 0.f;
-    if (in_lds) {
-      for (int k = ks; __any(k < ke); k += 4) {     // four neighbours per step out of LDS; dead slots carry weight 0
-        raw_t xv[4];
-        float w[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int kc = k + u < ke ? k + u : (ke > ks ? ke - 1 : 0);
-          const int slot = ke > ks ? s_el[kc] : 0;
-          w[u] = (k + u < ke) ? __int_as_float(s_u[slot].y) : 0.f;
-          xv[u] = *(const raw_t*)(s_data + slot * ROWB + gl * 16);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          float f[VEC];
-          V::unpack(xv[u], f);
-          axpy<VEC>(w[u], f, acc);
-        }
-      }
-    } else {
-      for (int k = ks; k < ke; ++k) {               // rare fallback: straight from global memory
-        const int2 e = a.lt_idx_w[e0 + k];
-        float f[VEC];
-        V::unpack(*(const raw_t*)(X + (int64_t)e.x * a.ldx + gl * VEC), f);
-        axpy<VEC>(__int_as_float(e.y), f, acc);
-      }
-    }
-    const float sdst = a.alpha * s_sd[lrc];
-    float y[VEC];
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) y[c] = sdst * acc[c];
-    if (NEPI >= 1) {
-      float f[VEC];
-      V::unpack(x0v, f);
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) y[c] = fmaf(a.beta, f[c], y[c]);
-    }
-    if (NEPI >= 2) {
-      float f[VEC];
-      V::unpack(x1v, f);
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) y[c] = fmaf(a.gamma, f[c], y[c]);
-    }
-    if (rvalid) *(raw_t*)(Y + (int64_t)row * a.ldy + gl * VEC) = V::pack(y);
-    if (NEPI >= 1) x0v = nx0;
-    if (NEPI >= 2) x1v = nx1;
-  }
-}
-
-template <typename T, int G>
-int launch_lds(const SpmmArgs& a, hipStream_t stream) {
-  const int64_t nt = ((int64_t)a.n_rows + kLdsRows - 1) / kLdsRows;
-  const int nblocks = (int)nt;
-  SpmmArgs b = a;
-  if (!a.X0 && a.X1) { b.X0 = a.X1; b.ldx0 = a.ldx1; b.beta = a.gamma; b.X1 = nullptr; b.ldx1 = 0; b.gamma = 0.f; }
-  if (b.X0 && b.X1) spmm_lds<T, G, 2><<<nblocks, kLdsBlock, 0, stream>>>(b, nblocks, g_tuning.flags);
-  else if (b.X0) spmm_lds<T, G, 1><<<nblocks, kLdsBlock, 0, stream>>>(b, nblocks, g_tuning.flags);
-  else spmm_lds<T, G, 0><<<nblocks, kLdsBlock, 0, stream>>>(b, nblocks, g_tuning.flags);
-  SG_HIP_TRY(hipGetLastError());
-  return SG_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
 // spmm_ring: the LDS-tile aggregation as a SOFTWARE PIPELINE with the reduction on the matrix cores (bf16 rows of 128 /
 // 256 channels on graphs that carry tile records; SG_TUNE_FLAGS bit 11 switches it off at graph creation or at launch).
 //
-// spmm_lds above pays, per tile and strictly one after the other, a metadata chain, the LDS-DMA round trip and the
-// reduction.  Here ONE persistent workgroup per CU (256 channels: 8 consumer + 4 producer wavefronts; 128 channels: 4 + 4,
-// two workgroups per CU) walks a stream of tiles (<= 16 rows, <= 56 distinct sources: csr_build.hip::build_ring_records)
+// An unpipelined LDS-tile kernel (retired: DESIGN.md, "Retired variants") paid, per tile and strictly one after the other,
+// a metadata chain, the LDS-DMA round trip and the reduction.  Here ONE persistent workgroup per CU (256 channels: 8
+// consumer + 4 producer wavefronts; 128 channels: 4 + 4, two workgroups per CU) walks a stream of tiles (<= 16 rows, <= 56 distinct sources: csr_build.hip::build_ring_records)
 // through a ring of D = 3 stages in LDS.  Iteration i, behind ONE s_barrier:
 //
 //   producers   tile i+D-1:  LDS-DMA of its distinct source rows and of its rows of the epilogue operands (the addresses
@@ -1615,75 +1457,6 @@ __global__ __launch_bounds__(kBlock) void spmm_quad_bf16(const SpmmArgs a) {
   }
 }
 
-// The same idea for bf16 rows of 8 / 16 / 32 channels (NV = 1 / 2 / 4 vectors of 16 bytes): one thread owns a whole ROW,
-// four neighbours in flight (NV loads each), CSR-order fma chain -- no LDS staging of the neighbour lists, no lane
-// groups.  Behind SG_TUNE_FLAGS bit 9 while it is being measured against spmm_rows<.., G = NV, ..>.
-template <int NV>
-__global__ __launch_bounds__(kBlock) void spmm_thread_rows_bf16(const SpmmArgs a) {
-  using V = Vt<bf16_tag>;
-  const uint16_t* __restrict__ X = (const uint16_t*)a.X;
-  const uint16_t* __restrict__ X0 = (const uint16_t*)a.X0;
-  const uint16_t* __restrict__ X1 = (const uint16_t*)a.X1;
-  uint16_t* __restrict__ Y = (uint16_t*)a.Y;
-  for (int row = blockIdx.x * kBlock + threadIdx.x; row < a.n_rows; row += gridDim.x * kBlock) {
-    const int k0 = a.rowptr[row], k1 = a.rowptr[row + 1];
-    float acc[NV * 8];
-#pragma unroll
-    for (int c = 0; c < NV * 8; ++c) acc[c] = 0.f;
-    for (int k = k0; k < k1; k += 4) {
-      u32x4 v[4][NV];
-      float w[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int kk = k + u < k1 ? k + u : k1 - 1;
-        int j;
-        if (a.idx_w) {
-          const int2 e = a.idx_w[kk];
-          j = e.x;
-          w[u] = __int_as_float(e.y);
-        } else {
-          j = a.idx[kk];
-          w[u] = a.scale_src ? a.scale_src[j] : 1.0f;
-        }
-#pragma unroll
-        for (int q = 0; q < NV; ++q) v[u][q] = *(const u32x4*)(X + (int64_t)j * a.ldx + q * 8);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (k + u < k1) {
-#pragma unroll
-          for (int q = 0; q < NV; ++q) {
-            float x[8];
-            V::unpack(v[u][q], x);
-#pragma unroll
-            for (int c = 0; c < 8; ++c) acc[q * 8 + c] = fmaf(w[u], x[c], acc[q * 8 + c]);
-          }
-        }
-    }
-    const float sd = a.alpha * (a.scale_dst ? a.scale_dst[row] : 1.0f);
-    const int64_t orow = a.row_id ? a.row_id[row] : row;
-#pragma unroll
-    for (int q = 0; q < NV; ++q) {
-      float y[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) y[c] = sd * acc[q * 8 + c];
-      if (X0) {
-        float x[8];
-        V::unpack(*(const u32x4*)(X0 + orow * a.ldx0 + q * 8), x);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) y[c] = fmaf(a.beta, x[c], y[c]);
-      }
-      if (X1) {
-        float x[8];
-        V::unpack(*(const u32x4*)(X1 + orow * a.ldx1 + q * 8), x);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) y[c] = fmaf(a.gamma, x[c], y[c]);
-      }
-      *(u32x4*)(Y + orow * a.ldy + q * 8) = V::pack(y);
-    }
-  }
-}
-
 template <typename T>
 __global__ __launch_bounds__(kBlock) void gather_rows_vec(const int32_t* __restrict__ rows, int64_t n,
                                                           const void* X, int64_t ldx, void* Y,
@@ -1752,12 +1525,9 @@ int launch_rows_epi(const SpmmArgs& a, hipStream_t stream) {
   constexpr int64_t esz = sizeof(typename Vt<T>::elem);
   const bool narrow = !(g_tuning.flags & kFlagWideAddr) && a.n_cols > 0 && a.n_cols < (1 << 24) &&
                       a.ldx * esz < (1 << 24) && a.n_cols * a.ldx * esz < ((int64_t)1 << 32);
-  const int cap = g_tuning.unroll == 4 || g_tuning.unroll == 6 || g_tuning.unroll == 8 ? g_tuning.unroll : default_cap<T, G, R>();
 #define SG_ROWS(NW, CP) spmm_rows<T, G, R, NEPI, NW, CP><<<nblocks, kBlock, 0, stream>>>(a, ch, nblocks, g_tuning.flags)
   if (!narrow) SG_ROWS(false, 8);          // > 4 GiB operands / > 16 M rows: rare, one variant
-  else if (cap == 4) SG_ROWS(true, 4);
-  else if (cap == 6) SG_ROWS(true, 6);
-  else SG_ROWS(true, 8);
+  else SG_ROWS(true, (default_cap<T, G, R>()));
 #undef SG_ROWS
   SG_HIP_TRY(hipGetLastError());
   return SG_OK;
@@ -1820,15 +1590,6 @@ int launch_typed_one(const SpmmArgs& a, hipStream_t stream) {
     return SG_OK;
   }
   const int nvec = a.C / VEC;
-  if (esz == 2 && (g_tuning.flags & kFlagThreadRows) && (nvec == 1 || nvec == 2 || nvec == 4)) {
-    int nb = (a.n_rows + kBlock - 1) / kBlock;
-    nb = nb > 256 * 64 ? 256 * 64 : nb;
-    if (nvec == 1) spmm_thread_rows_bf16<1><<<nb, kBlock, 0, stream>>>(a);
-    else if (nvec == 2) spmm_thread_rows_bf16<2><<<nb, kBlock, 0, stream>>>(a);
-    else spmm_thread_rows_bf16<4><<<nb, kBlock, 0, stream>>>(a);
-    SG_HIP_TRY(hipGetLastError());
-    return SG_OK;
-  }
   // Wide rows of a graph that carries mini-tiles: gather each distinct source row of 4 rows once.
   // Measured on the 1 M-vertex Morton-ordered mesh (tools/agg_bench.py, variants interleaved in one process):
   // it pays for fp32 rows of 2 KiB (C=512: 1.13 -> 0.97 ms plain, 1.40 -> 1.31 ms with an epilogue operand) and
@@ -1840,7 +1601,6 @@ int launch_typed_one(const SpmmArgs& a, hipStream_t stream) {
   const bool forced = tmin < 0 && row_bytes >= -tmin;
   const bool pays = tmin > 0 && sizeof(typename Vt<T>::elem) == 4 && row_bytes >= tmin &&
                     (row_bytes >= 2 * tmin || !(a.X0 || a.X1));
-  // LDS-tile kernel (opt-in while it is being measured: SG_TUNE_FLAGS bit 7): whole-row lane groups of 16 / 32 / 64 lanes
   if (!(g_tuning.flags & kFlagNoRing) && esz == 2 && a.lt_rec && a.lt_nrec > 0 && a.n_cols < ((int64_t)1 << 31)) {
     if (a.C == 128) return launch_ring<2>(a, stream);
     if (a.C == 256) return launch_ring<4>(a, stream);
@@ -1848,11 +1608,6 @@ int launch_typed_one(const SpmmArgs& a, hipStream_t stream) {
   if (!(g_tuning.flags & (kFlagNoRing | kFlagNoRingF32)) && esz == 4 && a.lt_rec && a.lt_nrec > 0 && a.n_cols < ((int64_t)1 << 31)) {
     int rc = SG_OK;
     if ((a.C == 128 || a.C == 256) && launch_ring_f32(a, stream, &rc)) return rc;
-  }
-  if ((g_tuning.flags & kFlagLdsTiles) && a.lt_uptr && a.ldx % VEC == 0 && a.n_cols < ((int64_t)1 << 31)) {
-    if (nvec == 16) return launch_lds<T, 16>(a, stream);
-    if (nvec == 32) return launch_lds<T, 32>(a, stream);
-    if (nvec == 64) return launch_lds<T, 64>(a, stream);
   }
   if (a.tile_uptr && (forced || pays) && !(g_tuning.flags & kFlagNoTiles)) {
     if (nvec > 16 && nvec <= 32) return launch_shared<T, 32, 1>(a, stream);
@@ -1870,43 +1625,26 @@ int launch_typed_one(const SpmmArgs& a, hipStream_t stream) {
   return launch_rows<T, 64, 4>(a, stream);
 }
 
-// Column slabs: sweep all rows once per slab of `slab` channels, so that the rows a sweep
-// keeps re-gathering (the neighbouring "lines" of the mesh) shrink to slab-wide segments
-// that stay L2-resident.
-template <typename T>
-int launch_typed(const SpmmArgs& a, hipStream_t stream) {
-  constexpr int VEC = Vt<T>::VEC;
-  const int slab = g_tuning.slab;
-  if (slab <= 0 || a.C <= slab || slab % VEC != 0) return launch_typed_one<T>(a, stream);
-  using elem_t = typename Vt<T>::elem;
-  for (int c0 = 0; c0 < a.C; c0 += slab) {
-    SpmmArgs s = a;
-    s.C = a.C - c0 < slab ? a.C - c0 : slab;
-    s.X = (const elem_t*)a.X + c0;
-    s.Y = (elem_t*)a.Y + c0;
-    if (a.X0) s.X0 = (const elem_t*)a.X0 + c0;
-    if (a.X1) s.X1 = (const elem_t*)a.X1 + c0;
-    int rc = launch_typed_one<T>(s, stream);
-    if (rc != SG_OK) return rc;
-  }
-  return SG_OK;
-}
-
 }  // namespace
 
 bool tiles_enabled() { return g_tuning.tiled_min_row_bytes != 0; }
-bool lds_tiles_enabled() { return (g_tuning.flags & kFlagLdsTiles) != 0; }
 bool ring_enabled() { return (g_tuning.flags & kFlagNoRing) == 0; }
 bool ring_f32_enabled() { return (g_tuning.flags & (kFlagNoRing | kFlagNoRingF32)) == 0; }
 
 int set_tuning(int knob, int value) {
   switch (knob) {
     case SG_TUNE_CHUNK_ROWS: g_tuning.chunk_rows = value; return SG_OK;
-    case SG_TUNE_FLAGS: g_tuning.flags = value; return SG_OK;
-    case SG_TUNE_UNROLL: g_tuning.unroll = value; return SG_OK;
-    case SG_TUNE_SLAB: g_tuning.slab = value; return SG_OK;
+    case SG_TUNE_FLAGS:
+      if (value & ~kFlagsKept) {
+        set_error("sg_tuning_set: SG_TUNE_FLAGS value %d sets bits 0x%x, which select nothing (bits 7 and 9 are retired)", value,
+                  (unsigned)(value & ~kFlagsKept));
+        return SG_ERR_INVALID;
+      }
+      g_tuning.flags = value;
+      return SG_OK;
     case SG_TUNE_TILED_MIN_ROW_BYTES: g_tuning.tiled_min_row_bytes = value; return SG_OK;
-    default: set_error("unknown tuning knob %d", knob); return SG_ERR_INVALID;
+    case 2: case 3: set_error("sg_tuning_set: knob %d is retired (value %d refused)", knob, value); return SG_ERR_INVALID;
+    default: set_error("sg_tuning_set: unknown tuning knob %d (value %d)", knob, value); return SG_ERR_INVALID;
   }
 }
 
@@ -1918,8 +1656,8 @@ int launch_spmm(const SpmmArgs& a_in, int dtype, hipStream_t stream) {
     a.tile_uniq_w = nullptr;
   }
   switch (dtype) {
-    case SG_F32: return launch_typed<float>(a, stream);
-    case SG_BF16: return launch_typed<bf16_tag>(a, stream);
+    case SG_F32: return launch_typed_one<float>(a, stream);
+    case SG_BF16: return launch_typed_one<bf16_tag>(a, stream);
     default: set_error("unsupported dtype %d", dtype); return SG_ERR_UNSUPPORTED;
   }
 }

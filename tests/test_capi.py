@@ -96,6 +96,38 @@ def test_block_and_trace_entry_points_without_gpu():
     assert lib.sg_tuning_set(capi.TUNE_BLOCK_PLANES, 1) == 0
 
 
+def test_tuning_set_refuses_retired_knobs_and_values():
+    """sg_tuning_set (no device needed): the retired knobs 2 and 3, SG_TUNE_FLAGS bits that select nothing (7 and 9 once
+    selected kernels) and the retired SG_TUNE_GEMM_TILE values 2 and 5 are refused with a message that names the knob and
+    the value; every kept knob accepts its default, which is also what this test leaves behind."""
+    lib = capi.load()
+    assert not hasattr(capi, "TUNE_UNROLL") and not hasattr(capi, "TUNE_SLAB")
+    refused = [(2, 4, (b"knob 2", b"4")), (3, 64, (b"knob 3", b"64")), (2, 0, (b"knob 2", b"0")), (3, 0, (b"knob 3", b"0")),
+               (capi.TUNE_FLAGS, 1 | 128, (b"SG_TUNE_FLAGS", b"129")), (capi.TUNE_FLAGS, 1 | 512, (b"SG_TUNE_FLAGS", b"513")),
+               (capi.TUNE_GEMM_TILE, 2, (b"SG_TUNE_GEMM_TILE", b"not 2")), (capi.TUNE_GEMM_TILE, 5, (b"SG_TUNE_GEMM_TILE", b"not 5"))]
+    for knob, value, words in refused:
+        assert lib.sg_tuning_set(knob, value) == -1, (knob, value)
+        msg = lib.sg_last_error()
+        assert all(w in msg for w in words), (knob, value, msg)
+    with pytest.raises(capi.SemigcnLibraryError, match="SG_TUNE_FLAGS"):
+        capi.tuning_set(capi.TUNE_FLAGS, 1 | 128)
+    assert lib.sg_tuning_set(capi.TUNE_FLAGS, 1 << 14) == -1 and lib.sg_tuning_set(capi.TUNE_GEMM_TILE, -1) == -1
+    # what the suite and the tools pass stays accepted
+    for flags in (1, 2, 4, 8, 16, 32, 64, 256, 2048, 4096, 8192, 1 | 2048, 1 | 4096):
+        assert lib.sg_tuning_set(capi.TUNE_FLAGS, flags) == 0, flags
+    for tile in (1, 3, 4):
+        assert lib.sg_tuning_set(capi.TUNE_GEMM_TILE, tile) == 0, tile
+    defaults = {capi.TUNE_CHUNK_ROWS: 0, capi.TUNE_FLAGS: 1, capi.TUNE_TILED_MIN_ROW_BYTES: 1024, capi.TUNE_GEMM_TILE: 0,
+                capi.TUNE_GRAPH_REORDER: 0, capi.TUNE_BLOCK_PLANES: 1,
+                capi.TUNE_F32_ENGINE: int(os.environ.get("SEMIGCN_F32_ENGINE") or 0),
+                capi.TUNE_BN_ROWS: int(os.environ.get("SEMIGCN_BN_ROWS") or 0)}
+    assert sorted(defaults) == [0, 1, 4, 5, 6, 7, 8, 9]            # the surviving knobs keep their numbers
+    for knob, value in defaults.items():
+        assert lib.sg_tuning_set(knob, value) == 0, (knob, lib.sg_last_error())
+    capi._sizes.cache_clear()
+    assert capi.gemm_tile_rows(256) == 128
+
+
 def test_comm_entry_points_without_gpu():
     """sg_comm_* / sg_halo_exchange / sg_part_run (csrc/comm.hip): the schedule entry's ctypes mirror has
     the library's size, and every entry point rejects a bad argument before RCCL or a device is touched."""

@@ -29,12 +29,15 @@ def main():
     ap.add_argument("--epilogue", default="0,1")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=4)
-    ap.add_argument("--variants", nargs="*", default=["ch=0,flags=1,unroll=0"])
+    ap.add_argument("--variants", nargs="*", default=["ch=0,flags=1"])
     ap.add_argument("--json", default=None)
     ap.add_argument("--blocks", type=int, default=1, help="operands are column blocks of [V, blocks*C] buffers (the in-model layout: 3)")
     ap.add_argument("--reorder", type=int, default=0, help="SG_TUNE_GRAPH_REORDER while the graph is created: 0 auto, 1 never, 2 always")
     a = ap.parse_args()
-    dev = torch.device("cuda:0")
+    for v in a.variants:
+        if "unroll=" in v or "slab=" in v:
+            ap.error(f"variant {v!r}: unroll= and slab= are retired (DESIGN.md, 'Retired variants')")
+    dev =torch.device("cuda:0")
     nu, nv = map(int, a.mesh.split("x"))
     m = synth.torus_mesh(nu, nv, permute=a.permute, masks=False)
     V, E = m.num_vertices, m.num_edges
@@ -44,8 +47,6 @@ def main():
         order, rank = reorder.morton_order(torch.from_numpy(m.vs).to(dev))
         ei = reorder.permute_edge_index(ei, rank)
     capi.tuning_set(capi.TUNE_GRAPH_REORDER, a.reorder)
-    if any("flags=" in v and int(dict(kv.split("=") for kv in v.split(","))["flags"]) & 128 for v in a.variants):
-        capi.tuning_set(capi.TUNE_FLAGS, 129)      # experimental LDS tile lists are only built on request
     torch.cuda.synchronize()
     import time
     t0 = time.perf_counter()
@@ -57,7 +58,7 @@ def main():
     variants = []
     for v in a.variants:
         d = dict(kv.split("=") for kv in v.split(","))
-        variants.append((v, int(d.get("ch", 0)), int(d.get("flags", 1)), int(d.get("unroll", 0)), int(d.get("slab", 0)), int(d.get("tmin", 1024))))
+        variants.append((v, int(d.get("ch", 0)), int(d.get("flags", 1)), int(d.get("tmin", 1024))))
     out = []
     for dt in a.dtypes.split(","):
         dtype = torch.float32 if dt == "fp32" else torch.bfloat16
@@ -74,11 +75,9 @@ def main():
             for nepi in map(int, a.epilogue.split(",")):
                 times = {v[0]: [] for v in variants}
                 for rnd in range(a.rounds + 1):
-                    for name, ch, flags, unroll, slab, tmin in variants:
+                    for name, ch, flags, tmin in variants:
                         capi.tuning_set(capi.TUNE_CHUNK_ROWS, ch)
                         capi.tuning_set(capi.TUNE_FLAGS, flags)
-                        capi.tuning_set(capi.TUNE_UNROLL, unroll)
-                        capi.tuning_set(capi.TUNE_SLAB, slab)
                         capi.tuning_set(capi.TUNE_TILED_MIN_ROW_BYTES, tmin)
                         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                         e0.record()

@@ -46,7 +46,7 @@ def main():
     dev = torch.device("cuda:0")
     M = a.V
     res = []
-    tot = {"mfma": 0.0, "mfma128": 0.0, "mfma64x256": 0.0, "mfma+moments": 0.0, "blas": 0.0, "best": 0.0, "ideal": 0.0}
+    tot = {"mfma": 0.0, "mfma128": 0.0,"mfma+moments": 0.0, "blas": 0.0, "best": 0.0, "ideal": 0.0}
     for name, N, K in products():
         A = torch.randn(M, K, device=dev).to(torch.bfloat16)
         B = (torch.randn(N, K, device=dev) / K ** 0.5).to(torch.bfloat16)
@@ -62,7 +62,6 @@ def main():
         variants = {
             "mfma": own(0),                       # the shipped tile choice
             "mfma128": own(1),                    # 128-row tiles always
-            "mfma64x256": own(2),                 # 64 x 256 tiles wherever N > 64
             "mfma+moments": own(0, True),
             "blas": lambda: torch.addmm(bias16, A, B.t(), out=out),
         }
