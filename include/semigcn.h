@@ -395,6 +395,65 @@ SG_API int sg_surface_self_pairs(const sg_surface* s, const float* vs, const int
                                  const int64_t* offsets, int64_t n_pairs, int64_t* pairs, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Ray casting and render results -- the first-hit query of an sg_surface and
+ * the small renderer on it: what util/render.py:19-45 (the pyvista turntable)
+ * and the coloured mask mesh of util/datamaker.py:161-171 show.  The rule --
+ * when a face is hit, at which t, which hit wins, the camera rays and the
+ * shading -- is specified in semigcn_amd/render.py ("The rule"): float64 on
+ * the float32 values, no fused multiply-add, closed comparisons (touching
+ * counts).  csrc/mesh_ray.hip.
+ *
+ * vs float32 [V,3] and faces int64 [F,3] are the arrays the surface was built
+ * from (the predicate reads them, not the surface's rounded copies) and F its
+ * face count.  A null pointer, a null surface, an F that is not the surface's,
+ * a negative N, width or height, t_min > t_max (or a NaN) or more than 2^31 - 1
+ * rays or pixels give SG_ERR_INVALID before the device is touched -- the sizes
+ * and the range first, before the surface is looked into, as n_pairs in
+ * sg_surface_self_pairs; N == 0 or zero pixels return SG_OK without a launch.
+ *
+ * sg_surface_raycast: for N rays origins / dirs float32 [N,3] and the closed
+ *   range [t_min, t_max]: t float32 [N] = the smallest float64 t at which the
+ *   rule finds a hit, rounded; face int32 [N] = the face hit, the lowest id on
+ *   an exact tie of t; bary_or_null float32 [N,2] = the weights of the face's
+ *   second and third vertex at the hit.  A miss, a ray with a NaN or an
+ *   infinite component and d = 0 give t = +inf, face = 0x7fffffff
+ *   (sg_surface_query's "no face") and a NaN bary row; the other rows are not
+ *   affected.  A row depends on its ray and the faces only, not on the order of
+ *   the rays or of the walk.  stats_dev int64 [2] (device): [0] = subtrees the
+ *   walk had to drop because its stack was full -- 0 for every tree
+ *   sg_surface_create builds; a caller that reads anything else must discard
+ *   the rows; [1] = leaves visited, summed over the rays (for profiles).
+ *   Asynchronous; integer atomics on stats only: two runs give identical bytes.
+ * sg_surface_render: the same rows for the width x height primary rays of a
+ *   camera, pixel (x, y) at row y * width + x, generated in the kernel.  cam
+ *   (host, 14 doubles, read before the call returns) = eye, right, up, forward
+ *   (orthonormal), tx, ty: the tangents of the half view angles, or with
+ *   ortho != 0 the half extents of the view.  Equal to sg_surface_raycast on
+ *   the rays of the rule, bit for bit.
+ * sg_shade_hits: rgb uint8 [n,3] from face / bary [n] rows and the ray
+ *   directions: dirs_or_null float32 [n,3], or with a null dirs the camera
+ *   (cam, ortho, width, height as above, n = width * height).  A row without a
+ *   face takes `background`; the others color / face_colors uint8 [F,3] /
+ *   the interpolated scalars float32 [V] through the five-stop map over
+ *   [vmin, vmax], by mode, times the two-sided flat head-light intensity
+ *   ambient + (1 - ambient) |d.n| / sqrt((d.d)(n.n)).  color and background
+ *   are 0xRRGGBB.  Asynchronous, no atomics.
+ * ------------------------------------------------------------------------- */
+#define SG_SHADE_CONSTANT 0
+#define SG_SHADE_FACE 1
+#define SG_SHADE_SCALAR 2
+SG_API int sg_surface_raycast(const sg_surface* s, const float* vs, const int64_t* faces, int64_t F, const float* origins,
+                              const float* dirs, int64_t N, double t_min, double t_max, float* t, int32_t* face,
+                              float* bary_or_null, int64_t* stats_dev, void* stream);
+SG_API int sg_surface_render(const sg_surface* s, const float* vs, const int64_t* faces, int64_t F, const double* cam,
+                             int ortho, int64_t width, int64_t height, double t_min, double t_max, int32_t* face, float* t,
+                             float* bary, int64_t* stats_dev, void* stream);
+SG_API int sg_shade_hits(const float* vs, int64_t V, const int64_t* faces, int64_t F, const int32_t* face, const float* bary,
+                         const float* dirs_or_null, const double* cam, int ortho, int64_t width, int64_t height, int64_t n,
+                         int mode, uint32_t color, const uint8_t* face_colors, const float* scalars, double vmin, double vmax,
+                         uint32_t background, double ambient, uint8_t* rgb, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Area-weighted surface samples and the reductions of the two-sided sampled
  * distance (Hausdorff, Chamfer, normal consistency): what MeshLab's
  * hausdorff_distance filter is used for, and what the reference's one-sided

@@ -8,9 +8,10 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import math
 from array import array as _array
 import os
-from ctypes import POINTER, byref, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
 from typing import Optional
 
 import torch  # imported first so that libamdhip64.so.7 resolves to the copy torch already loaded
@@ -199,6 +200,13 @@ _SIGNATURES = {
     "sg_surface_query": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_surface_self_count": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sg_surface_self_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "sg_surface_raycast": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_double, c_double,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_surface_render": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int64, c_double, c_double,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sg_shade_hits": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                              c_int64, c_int64, c_int, c_uint32, c_void_p, c_void_p, c_double, c_double, c_uint32, c_double,
+                              c_void_p, c_void_p]),
     "sg_mesh_distance_reduce": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                         c_void_p]),
     "sg_sampler_create": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_void_p)]),
@@ -1472,6 +1480,129 @@ class SurfaceHandle(_OwnedHandle):
             _check(load().sg_surface_self_pairs(self._h, _ptr(vs), _ptr(faces), self.num_faces, _ptr(offsets), int(n_pairs),
                                                 _ptr(pairs), _stream(vs)), "sg_surface_self_pairs")
         return pairs
+
+    def ray_cast(self, vs: torch.Tensor, faces: torch.Tensor, origins: torch.Tensor, dirs: torch.Tensor, t_min: float = 0.0,
+                 t_max: float = math.inf, with_bary: bool = True):
+        """(t float32 [N], face int32 [N], bary float32 [N, 2] or None, stats int64 [2]) of sg_surface_raycast for the rays
+        origins / dirs float32 [N, 3], on the device; stats = (dropped subtrees, leaf visits), not read here."""
+        self._self_args(vs, faces)
+        for x, n in ((origins, "origins"), (dirs, "directions")):
+            _require_device(x, n)
+            if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 3 or not x.is_contiguous():
+                raise SemigcnLibraryError(f"{n} must be contiguous float32 [N, 3], got {x.dtype} {tuple(x.shape)}")
+            if x.device != self.device:
+                raise SemigcnLibraryError(f"{n} on {x.device}, surface on {self.device}")
+        if origins.shape != dirs.shape:
+            raise SemigcnLibraryError(f"{origins.shape[0]} origins and {dirs.shape[0]} directions")
+        N = origins.shape[0]
+        t = torch.empty(N, dtype=torch.float32, device=self.device)
+        face = torch.empty(N, dtype=torch.int32, device=self.device)
+        bary = torch.empty((N, 2), dtype=torch.float32, device=self.device) if with_bary else None
+        stats = torch.zeros(2, dtype=torch.int64, device=self.device)
+        with _on_device(self.device):
+            _check(load().sg_surface_raycast(self._h, _ptr(vs), _ptr(faces), self.num_faces, _ptr(origins), _ptr(dirs), N,
+                                             float(t_min), float(t_max), _ptr(t), _ptr(face), _ptr(bary), _ptr(stats),
+                                             _stream(vs)), "sg_surface_raycast")
+        return t, face, bary, stats
+
+    def render(self, vs: torch.Tensor, faces: torch.Tensor, cam, ortho: bool, width: int, height: int, t_min: float = 0.0,
+               t_max: float = math.inf):
+        """(face int32 [H, W], t float32 [H, W], bary float32 [H, W, 2], stats int64 [2]) of sg_surface_render; ``cam``: the
+        14 floats eye, right, up, forward, tx, ty."""
+        self._self_args(vs, faces)
+        cam = [float(x) for x in cam]
+        if len(cam) != 14:
+            raise SemigcnLibraryError(f"cam must hold 14 values (eye, right, up, forward, tx, ty), got {len(cam)}")
+        width, height = int(width), int(height)
+        if width < 0 or height < 0:
+            raise SemigcnLibraryError(f"negative image size {width} x {height}")
+        face = torch.empty((height, width), dtype=torch.int32, device=self.device)
+        t = torch.empty((height, width), dtype=torch.float32, device=self.device)
+        bary = torch.empty((height, width, 2), dtype=torch.float32, device=self.device)
+        stats = torch.zeros(2, dtype=torch.int64, device=self.device)
+        with _on_device(self.device):
+            _check(load().sg_surface_render(self._h, _ptr(vs), _ptr(faces), self.num_faces, (c_double * 14)(*cam),
+                                            int(bool(ortho)), width, height, float(t_min), float(t_max), _ptr(face), _ptr(t),
+                                            _ptr(bary), _ptr(stats), _stream(vs)), "sg_surface_render")
+        return face, t, bary, stats
+
+
+def check_walk_stats(stats: torch.Tensor, what: str, *counts: torch.Tensor):
+    """The leaf visits of a ray walk from its stats int64 [2]; raises when the walk dropped a subtree.  ``counts``: scalar
+    integer tensors on the same device, read in the same (the one) synchronisation and returned behind the visits as a
+    tuple."""
+    dropped, visits, *more = torch.cat([stats] + [c.reshape(1).to(torch.int64) for c in counts]).tolist()
+    if dropped:
+        raise SemigcnLibraryError(f"{what}: the walk dropped {dropped} subtrees on a full stack; the rows are not valid")
+    return (visits, *more) if counts else visits
+
+
+SHADE_MODES = {"constant": 0, "face": 1, "scalar": 2}       # SG_SHADE_*
+
+
+def _rgb24(c, name: str) -> int:
+    c = [int(x) for x in c]
+    if len(c) != 3 or min(c) < 0 or max(c) > 255:
+        raise SemigcnLibraryError(f"{name} must be three levels in 0 .. 255, got {c}")
+    return c[0] << 16 | c[1] << 8 | c[2]
+
+
+def shade_hits(vs: torch.Tensor, faces: torch.Tensor, face: torch.Tensor, bary: Optional[torch.Tensor], *,
+               dirs: Optional[torch.Tensor] = None, cam=None, ortho: bool = False, size=None, color=(255, 165, 0),
+               face_colors: Optional[torch.Tensor] = None, scalars: Optional[torch.Tensor] = None, vmin: float = 0.0,
+               vmax: float = 1.0, background=(255, 255, 255), ambient: float = 0.25) -> torch.Tensor:
+    """rgb uint8 [n, 3] of sg_shade_hits for the rows face int32 [n] / bary float32 [n, 2] of a walk over (vs, faces): the
+    ray directions come from ``dirs`` float32 [n, 3] or from the camera (``cam`` 14 floats, ``ortho``, ``size`` = (width,
+    height), n = width * height).  ``face_colors`` uint8 [F, 3] or ``scalars`` float32 [V] choose the mode; neither:
+    ``color``."""
+    vs, faces = _vs_arg(vs), _faces_arg(faces)
+    tensors = [(vs, "vs"), (faces, "faces"), (face, "face"), (bary, "bary"), (dirs, "dirs"), (face_colors, "face_colors"),
+               (scalars, "scalars")]
+    for x, n in tensors:
+        if x is not None:
+            _require_device(x, n)
+            if x.device != vs.device:
+                raise SemigcnLibraryError(f"{n} on {x.device}, vs on {vs.device}")
+            if not x.is_contiguous():
+                raise SemigcnLibraryError(f"{n} must be contiguous")
+    n = face.numel()
+    if face.dtype != torch.int32:
+        raise SemigcnLibraryError(f"face must be int32, got {face.dtype}")
+    if bary is not None and (bary.dtype != torch.float32 or bary.numel() != 2 * n):
+        raise SemigcnLibraryError(f"bary must be float32 [{n}, 2], got {bary.dtype} {tuple(bary.shape)}")
+    if face_colors is not None and scalars is not None:
+        raise SemigcnLibraryError("give face_colors or scalars, not both")
+    mode = "constant"
+    if face_colors is not None:
+        mode = "face"
+        if face_colors.dtype != torch.uint8 or tuple(face_colors.shape) != (faces.shape[0], 3):
+            raise SemigcnLibraryError(f"face_colors must be uint8 [{faces.shape[0]}, 3], got {face_colors.dtype} "
+                                      f"{tuple(face_colors.shape)}")
+    if scalars is not None:
+        mode = "scalar"
+        if scalars.dtype != torch.float32 or scalars.numel() != vs.shape[0] or bary is None:
+            raise SemigcnLibraryError(f"scalars must be float32 [{vs.shape[0]}] and come with bary, got {scalars.dtype} "
+                                      f"{tuple(scalars.shape)}")
+    width = height = 0
+    cam_arg = None
+    if dirs is not None:
+        if dirs.dtype != torch.float32 or tuple(dirs.shape) != (n, 3):
+            raise SemigcnLibraryError(f"dirs must be float32 [{n}, 3], got {dirs.dtype} {tuple(dirs.shape)}")
+    else:
+        if cam is None or size is None:
+            raise SemigcnLibraryError("shade_hits: give dirs, or cam and size")
+        cam = [float(x) for x in cam]
+        width, height = int(size[0]), int(size[1])
+        if len(cam) != 14 or width * height != n:
+            raise SemigcnLibraryError(f"cam must hold 14 values and size {width} x {height} the {n} rows")
+        cam_arg = (c_double * 14)(*cam)
+    rgb = torch.empty((n, 3), dtype=torch.uint8, device=vs.device)
+    with _on_device(vs.device):
+        _check(load().sg_shade_hits(_ptr(vs), vs.shape[0], _ptr(faces), faces.shape[0], _ptr(face), _ptr(bary), _ptr(dirs),
+                                    cam_arg, int(bool(ortho)), width, height, n, SHADE_MODES[mode], _rgb24(color, "color"),
+                                    _ptr(face_colors), _ptr(scalars), float(vmin), float(vmax),
+                                    _rgb24(background, "background"), float(ambient), _ptr(rgb), _stream(vs)), "sg_shade_hits")
+    return rgb
 
 
 def mesh_distance_reduce(q: torch.Tensor, gt_vs: torch.Tensor, q_org: Optional[torch.Tensor] = None, eps: float = 0.05,

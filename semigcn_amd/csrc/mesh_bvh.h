@@ -1,5 +1,5 @@
-// The surface hierarchy as its traversals see it: what mesh_dist.hip (build, closest-point query) and mesh_isect.hip
-// (self-overlap query) both need to know about an sg_surface and the layout of its nodes.  Nothing else is shared.
+// The surface hierarchy as its traversals see it: what mesh_dist.hip (build, closest-point query), mesh_isect.hip
+// (self-overlap query) and mesh_ray.hip (first-hit query) need to know about an sg_surface and the layout of its nodes.  Nothing else is shared.
 #pragma once
 #include "mesh_common.h"
 

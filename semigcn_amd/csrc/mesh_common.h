@@ -1,9 +1,9 @@
-// What the mesh stages (mesh_prep, mesh_smooth, mesh_fill, mesh_parts, mesh_manifold, mesh_remesh, mesh_dist, mesh_isect, mesh_fair, mesh_sample, mesh_denoise) share on the host
+// What the mesh stages (mesh_prep, mesh_smooth, mesh_fill, mesh_parts, mesh_manifold, mesh_remesh, mesh_dist, mesh_isect, mesh_fair, mesh_sample, mesh_denoise, mesh_ray) share on the host
 // side: typed device buffers that own their memory, the launch geometry, the bit count behind the radix-sort ranges, the
 // exclusive scan, and the kernels and the one device helper that were literal copies.  The rule that goes with it: device
 // memory of a plan or of a call is a typed member or local that frees itself -- never a raw pointer on a hand-kept free list.
-// No floating-point code belongs here: mesh_isect.hip, mesh_remesh.hip, mesh_manifold.hip, mesh_fair.hip, mesh_sample.hip and
-// mesh_denoise.hip are built with -ffp-contract=off, the others not.
+// No floating-point code belongs here: mesh_isect.hip, mesh_remesh.hip, mesh_manifold.hip, mesh_fair.hip, mesh_sample.hip,
+// mesh_denoise.hip and mesh_ray.hip are built with -ffp-contract=off, the others not.
 #pragma once
 #include <hipcub/hipcub.hpp>
 

@@ -74,6 +74,14 @@ from .mesh_common import device_tensor, read_obj, vs_faces
 EPS_SIMULATED, EPS_REAL = 0.05, 1.0
 
 
+class Hits(NamedTuple):
+    """What ``Surface.ray_cast`` returns, one row per ray; a ray that hits nothing has ``t = inf``, ``face = 0x7fffffff`` and
+    a NaN ``bary`` row."""
+    t: torch.Tensor           # float32 [N]: the hit is at origin + t * direction
+    face: torch.Tensor        # int32 [N]: the face hit
+    bary: torch.Tensor        # float32 [N, 2]: the weights of the face's second and third vertex at the hit
+
+
 class Surface:
     """The triangles of one surface, with their hierarchy built once on the device; ``query`` then scores any number
     of point sets against it.  Open and non-manifold surfaces are fine (the reference loads org with manifold=False)."""
@@ -95,6 +103,29 @@ class Surface:
         if pts.device != self.device:
             pts = pts.to(self.device)
         return self._h.query(pts, signed=signed)
+
+    def ray_cast(self, origins, directions, t_min: float = 0.0, t_max: float = math.inf, with_visits: bool = False):
+        """The first hit of every ray ``origins[i] + t * directions[i]``, ``t`` in the closed range ``[t_min, t_max]``, by
+        the rule of ``semigcn_amd.render`` ("The rule"): ``Hits`` with the smallest ``t``, the lowest face id on an exact tie;
+        the directions need not be unit vectors (``t`` counts in their length).  A miss, a ray with a NaN or an infinite
+        component and a zero direction get ``t = inf``, ``face = 0x7fffffff`` and a NaN ``bary`` row, and leave the other rows
+        alone: test ``torch.isinf(t)`` before indexing with ``face``.  ``with_visits``: ``(Hits, leaves visited)``, the visits
+        summed over the rays, for profiles.  One host synchronisation (the walk's own check that it dropped no subtree)."""
+        o, d = mesh_common.points(origins).to(self.device), mesh_common.points(directions).to(self.device)
+        if o.shape != d.shape:
+            raise ValueError(f"{o.shape[0]} origins and {d.shape[0]} directions")
+        t, face, bary, stats = self._h.ray_cast(self.vs, self.faces, o, d, t_min, t_max)
+        visits = capi.check_walk_stats(stats, "Surface.ray_cast")
+        return (Hits(t, face, bary), visits) if with_visits else Hits(t, face, bary)
+
+    def camera_cast(self, cam, ortho: bool, width: int, height: int, t_min: float = 0.0, t_max: float = math.inf):
+        """``ray_cast`` on the ``width x height`` primary rays of a camera, generated on the device (``semigcn_amd.render``,
+        "Camera rays"; ``cam``: the 14 values of ``render.Camera.params``): ``(Hits`` with [H, W] rows, leaves visited,
+        pixels that see a face``)``.  What ``render.render`` is built on.  The same check and the same one synchronisation
+        as ``ray_cast``; the two counts are read with it."""
+        face, t, bary, stats = self._h.render(self.vs, self.faces, cam, ortho, width, height, t_min, t_max)
+        visits, seen = capi.check_walk_stats(stats, "Surface.camera_cast", (face != capi.NO_FACE).sum())
+        return Hits(t, face, bary), visits, seen
 
     def close(self):
         self._h.close()
