@@ -5,7 +5,30 @@ network, an irregular loop, and the command line.
 
 Shapes: n = 3 and n = 4 (the two special patches); ~200 loops of 4 .. 8 edges (the per-loop offset scans, many loops per
 block); one loop of >= 300 edges (the pointer jumping crosses a 64-lane wave and a 256-thread block, the arc-length scan
-takes more than one chunk); two loops of 1100 edges (longer than a 1024-thread block, 175 rings)."""
+takes more than one chunk); two loops of 1100 edges (longer than a 1024-thread block, 175 rings).
+
+The offset tables at their edges (meshes from tests/holes_fixtures.py, whose premises tests/test_holes_fixtures.py pins on
+the CPU, among them that these fixtures tell the kernel's offset search from one that takes the first of equal offsets):
+
+  fans(S13), caps None / 20 / 9 / 3 / 2   S13 = [3, 40, 3, 9, 10, 3, 40, 15, 16, 21, 22, 4, 3].  A triangle adds a face but no
+                      vertex and no ring table, a loop over the cap adds nothing: runs of equal entries in the per-loop
+                      vertex, face and ring offsets, first, last and between filled loops, and a loop either side of every
+                      change of the ring count.  Cap 3: faces without any ring table (Vn = 0, Fn = 4); cap 2: nothing.
+  fans([40, 3, 9, 40]), cap 20            the open loops first and last.
+  fans(S13, perm=5), caps None / 20       vertex ids shuffled: another loop order, loops interleaved in the sorted boundary.
+  one FillPlan at 20, 3, None, 2          the tables shrink to faces only, grow to everything, shrink to nothing.
+  L = 255, 256, 257, 1500 loops of 3 .. 23 edges, caps None / 9     the per-loop kernels run over L + 1 entries: the last
+                      single block, the first second block, one more, and six blocks.
+  one loop of 255, 256, 257, 511, 512, 513, 1024, 1025 edges        a whole chunk of the arc-length scan, and the pointer
+                      jumping's round count at a power of two, one less, one more.
+  coincident()        zero-length segments first, two in a row and closing (the ``seg > 0`` branch, the wrap to the
+                      perimeter), a loop of perimeter 0 (its new vertices are its point bit for bit), a loop 1e4 away.
+
+Positions are held to ``position_bound``, 2^-23 max|coordinate| (it was 1e-5 x the box diagonal, about 250 times as much).
+Measured worst error as a fraction of that bound on the MI355X: tetrahedron, octahedron 0; many_small 0.35; one_large 0.35;
+long_strip 0.36; fans(S13) 0.43 at caps None, 20, 9 and for the permuted ids and the one plan; fans([40, 3, 9, 40]) 0.13;
+L = 255 .. 1500 loops 0.27; single loops 0.44 .. 0.46 (5.7e-8 .. 6.0e-8 against 1.3e-7); coincident 0.41 (4.9e-4 against
+1.2e-3, set by the far loop), its two loops near the origin 0.06 of their own bound (2.7e-8 against 4.7e-7)."""
 import functools
 import json
 
@@ -13,6 +36,7 @@ import numpy as np
 import pytest
 import torch
 
+import holes_fixtures as HF
 import holes_oracle as HO
 import prepare_oracle as PO
 from semigcn_amd import synth
@@ -105,6 +129,15 @@ def diagonal(vs):
     return float(np.linalg.norm(vs.max(0).astype(np.float64) - vs.min(0).astype(np.float64)))
 
 
+def position_bound(vs):
+    """2^-23 max|coordinate|.  Both sides are float64 functions of the same float32 inputs.  The device rounds once to float32:
+    at most half an ulp, 2^-24 |x|, and a new vertex is a convex combination of loop vertices, so |x| <= max|coordinate|.
+    The float64 sums differ by their order only, n 2^-53 relative: 2^-29 of that half ulp at n = 2^20.  The other half ulp
+    is the margin for it (tests/test_holes_fixtures.py: another float64 order takes 0.41 .. 0.46 of the bound, float32 arc
+    lengths miss it)."""
+    return 2.0 ** -23 * float(np.abs(vs).max())
+
+
 # ---- loops -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(CASES))
 def test_loops_equal_the_serial_walk(name):
@@ -171,8 +204,7 @@ def test_unorderable_boundary_raises():
 # ---- raw construction --------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(CASES))
 def test_raw_construction_equals_the_oracle(name):
-    """Faces exactly.  Positions: the arc lengths are float64 on both sides, what remains is a handful of float32 roundings
-    on coordinates, of order 1e-7 x their magnitude; the bound 1e-5 x the box diagonal leaves two decades."""
+    """Faces exactly.  Positions: float64 on both sides and one rounding to float32 on the device, within ``position_bound``."""
     from semigcn_amd import holes
     vs, faces, (w_vs, w_faces, w_inserted, w_filled, loops) = case(name)
     V, F = vs.shape[0], faces.shape[0]
@@ -189,7 +221,7 @@ def test_raw_construction_equals_the_oracle(name):
     assert np.array_equal(out.filled.cpu().numpy(), w_filled) and w_filled.all()
     assert len(out.loops) == len(loops)
     err = float(np.abs(g_vs[V:].astype(np.float64) - w_vs[V:]).max()) if w_vs.shape[0] > V else 0.0
-    tol = 1e-5 * diagonal(vs)
+    tol = position_bound(vs)
     print(f"{name}: {w_vs.shape[0] - V} new vertices, {w_faces.shape[0] - F} new faces, max|err| {err:.3e}, bound {tol:.3e}")
     assert err <= tol
     if name == "tetrahedron":
@@ -229,7 +261,7 @@ def test_max_hole_edges():
     w_vs, w_faces, _, w_filled, _ = HO.fill_holes(vs, faces, max_hole_edges=20)
     assert np.array_equal(capped.faces.cpu().numpy(), w_faces) and w_filled.tolist() == capped.filled.cpu().tolist()
     assert capped.vs.shape[0] == V + 12 // 2 + 1 == w_vs.shape[0]                     # rings [12, 6, 1]
-    assert np.abs(capped.vs.cpu().numpy().astype(np.float64) - w_vs).max() <= 1e-5 * diagonal(vs)
+    assert np.abs(capped.vs.cpu().numpy().astype(np.float64) - w_vs).max() <= position_bound(vs)
     rest = holes.boundary_loops(capped.faces, capped.vs.shape[0])
     assert rest.sizes.cpu().tolist() == [38]
     assert not bool(holes.fill_holes((vs, faces), max_hole_edges=11, fair_steps=0).filled.any())
@@ -241,7 +273,7 @@ def test_max_hole_edges():
 
 def test_plan_again_on_the_same_plan():
     """``plan`` drops the sizes of the call before it: uncapped, capped at 20, uncapped again on ONE FillPlan, each emit against
-    the oracle result test_max_hole_edges asserts (faces and ``filled`` exactly, positions within its 1e-5 x diagonal)."""
+    the oracle result test_max_hole_edges asserts (faces and ``filled`` exactly, positions within ``position_bound``)."""
     from semigcn_amd import capi
     vs, faces, uncapped = case("planar")
     V = vs.shape[0]
@@ -258,11 +290,148 @@ def test_plan_again_on_the_same_plan():
             filled = plan.emit(d_vs, new_vs, new_faces)
             assert np.array_equal(new_faces.cpu().numpy(), w_faces[faces.shape[0]:])
             assert np.array_equal(filled.cpu().numpy(), w_filled)
-            assert np.abs(new_vs.cpu().numpy().astype(np.float64) - w_vs[V:]).max() <= 1e-5 * diagonal(vs)
+            assert np.abs(new_vs.cpu().numpy().astype(np.float64) - w_vs[V:]).max() <= position_bound(vs)
         assert w_filled.all() and Vn > 12 // 2 + 1                  # the last round filled the border loop as well
     finally:
         torch.cuda.current_stream().synchronize()                   # the plan's buffers are freed with it
         plan.close()
+
+
+# ---- the offset tables at their edges ----------------------------------------------------------------------------------
+def cycling(L):
+    return [3 + i % 21 for i in range(L)]
+
+
+FANS = {"s13": lambda: HF.fans(HF.S13), "s13_perm": lambda: HF.fans(HF.S13, perm=5), "ends_open": lambda: HF.fans([40, 3, 9, 40]),
+        "coincident": lambda: HF.coincident()[:2]}
+
+
+@functools.lru_cache(maxsize=None)
+def fan_case(name, cap=None):
+    """(vs, faces, the oracle's raw fill at ``cap``) of FANS[name], of "single<n>" or of "many<L>": computed once, read-only."""
+    if name.startswith("single"):
+        vs, faces = HF.fans([int(name[6:])])
+    elif name.startswith("many"):
+        vs, faces = HF.fans(cycling(int(name[4:])))
+    else:
+        vs, faces = FANS[name]()
+    want = HO.fill_holes(vs, faces, cap)
+    for a in (vs, faces) + want[:4]:
+        a.setflags(write=False)
+    return vs, faces, want
+
+
+def check_patches(label, vs, faces, want, new_vs, new_faces, filled):
+    """New faces and ``filled`` exactly, new positions finite and within ``position_bound``; returns and prints the error."""
+    w_vs, w_faces, _, w_filled, _ = want
+    V, F = vs.shape[0], faces.shape[0]
+    assert tuple(new_vs.shape) == (w_vs.shape[0] - V, 3) and tuple(new_faces.shape) == (w_faces.shape[0] - F, 3)
+    assert np.array_equal(new_faces.cpu().numpy(), w_faces[F:])
+    assert np.array_equal(filled.cpu().numpy(), w_filled)
+    g = new_vs.cpu().numpy()
+    assert np.isfinite(g).all()
+    err = float(np.abs(g.astype(np.float64) - w_vs[V:]).max()) if g.shape[0] else 0.0
+    tol = position_bound(vs)
+    print(f"{label}: {g.shape[0]} new vertices, {new_faces.shape[0]} new faces, max|err| {err:.3e} = {err / tol:.2f} of the "
+          f"bound {tol:.3e}")
+    assert err <= tol
+    return err
+
+
+def check_fill(name, cap):
+    """``fill_holes`` without fairing against the oracle: loops the serial walk, faces, ``filled``, ``inserted`` and sizes
+    exactly, the originals bit for bit, positions within the bound, and the loops that stay open exactly the unfilled ones."""
+    from semigcn_amd import holes
+    vs, faces, want = fan_case(name, cap)
+    w_vs, w_faces, w_inserted, w_filled, loops = want
+    V, F = vs.shape[0], faces.shape[0]
+    out = holes.fill_holes((dev(vs), dev(faces)), max_hole_edges=cap, fair_steps=0)
+    ptr, verts = HO.loops_csr(loops)
+    assert np.array_equal(out.loops.ptr.cpu().numpy(), ptr) and np.array_equal(out.loops.verts.cpu().numpy(), verts)
+    assert (out.num_original_vertices, out.num_original_faces) == (V, F)
+    assert np.array_equal(out.faces[:F].cpu().numpy(), faces)
+    assert np.array_equal(out.vs[:V].cpu().numpy().view(np.uint32), vs.view(np.uint32))
+    assert np.array_equal(out.inserted.cpu().numpy(), w_inserted)
+    check_patches(f"{name} cap {cap}", vs, faces, want, out.vs[V:], out.faces[F:], out.filled)
+    rest = holes.boundary_loops(out.faces, out.vs.shape[0])
+    open_loops = [l for l, f in zip(loops, w_filled) if not f]
+    assert rest.sizes.cpu().tolist() == [len(l) for l in open_loops]
+    assert np.array_equal(rest.verts.cpu().numpy(), HO.loops_csr(open_loops)[1])
+    return out, want
+
+
+@pytest.mark.parametrize("cap", [None, 20, 9, 3, 2])
+def test_loops_that_add_nothing_between_filled_ones(cap):
+    """S13: triangles (a face, no vertex, no ring table) and, under a cap, open loops (nothing at all) before, between and
+    after filled loops: runs of equal entries in all three offset tables.  Cap 3 fills triangles only (faces without a ring
+    table), cap 2 nothing."""
+    out, want = check_fill("s13", cap)
+    V, F = fan_case("s13", cap)[0].shape[0], fan_case("s13", cap)[1].shape[0]
+    assert (out.vs.shape[0] - V, out.faces.shape[0] - F) == HF.S13_COUNTS[cap]
+    assert out.filled.cpu().tolist() == [cap is None or n <= cap for n in HF.S13]
+
+
+def test_open_loops_first_and_last():
+    out, _ = check_fill("ends_open", 20)
+    assert out.filled.cpu().tolist() == [False, True, True, False]
+
+
+@pytest.mark.parametrize("cap", [None, 20])
+def test_loops_interleaved_in_id_space(cap):
+    _, (_, _, _, _, loops) = check_fill("s13_perm", cap)
+    assert [len(l) for l in loops] != HF.S13 and sorted(len(l) for l in loops) == sorted(HF.S13)
+
+
+def test_one_plan_through_four_caps():
+    """20, 3, None, 2 on ONE FillPlan: tables that shrink to faces only, grow to everything and shrink to nothing."""
+    from semigcn_amd import capi
+    vs, faces = fan_case("s13", None)[:2]
+    V = vs.shape[0]
+    d_vs = dev(vs)
+    with capi.FillPlan(dev(faces), V) as plan:
+        for cap in (20, 3, None, 2):
+            want = fan_case("s13", cap)[2]
+            Vn, Fn = plan.plan(cap)
+            assert (Vn, Fn) == HF.S13_COUNTS[cap]
+            new_vs = torch.empty((Vn, 3), dtype=torch.float32, device=DEV)
+            new_faces = torch.empty((Fn, 3), dtype=torch.int64, device=DEV)
+            filled = plan.emit(d_vs, new_vs, new_faces)
+            check_patches(f"one plan, cap {cap}", vs, faces, want, new_vs, new_faces, filled)
+        torch.cuda.current_stream().synchronize()                   # the plan's buffers are freed with it
+
+
+@pytest.mark.parametrize("cap", [None, 9])
+@pytest.mark.parametrize("L", [255, 256, 257, 1500])
+def test_many_loops_across_a_block_of_the_per_loop_kernels(L, cap):
+    """One thread per loop over L + 1 entries: L = 255 is the last single block, 256 the first with a second one."""
+    out, want = check_fill(f"many{L}", cap)
+    assert len(out.loops) == L and int(out.filled.sum()) == sum(cap is None or n <= cap for n in cycling(L))
+
+
+@pytest.mark.parametrize("n", list(HF.SINGLE_COUNTS))
+def test_single_loop_at_a_chunk_and_at_a_power_of_two(n):
+    """n = 256: exactly one chunk of the arc-length scan; 256, 512, 1024: the pointer jumping's ``span < nb`` round count at
+    a power of two, with one less and one more."""
+    out, _ = check_fill(f"single{n}", None)
+    vs, faces = fan_case(f"single{n}")[:2]
+    assert (out.vs.shape[0] - vs.shape[0], out.faces.shape[0] - faces.shape[0]) == HF.SINGLE_COUNTS[n]
+    assert HO.half_edge_stats(out.faces.cpu().numpy()) == (1, 0)
+
+
+def test_zero_length_segments_and_a_loop_of_perimeter_zero():
+    out, (w_vs, _, _, _, loops) = check_fill("coincident", None)
+    vs = fan_case("coincident")[0]
+    V = vs.shape[0]
+    first = V + sum(HO.ring_sizes(24)[1:])
+    mine = out.vs[first:first + sum(HO.ring_sizes(12)[1:])].cpu().numpy()
+    assert mine.shape[0] == 7 and np.array_equal(mine.view(np.uint32), np.repeat(vs[loops[1][:1]], 7, 0).view(np.uint32))
+    assert bool(torch.isfinite(out.vs).all())
+    # the loops near the origin on their own: their bound is 1e4 times tighter than the one the far loop sets
+    near = np.arange(V, first + 7)
+    tol = 2.0 ** -23 * float(np.abs(vs[loops[0] + loops[1]]).max())
+    err = float(np.abs(out.vs.cpu().numpy()[near].astype(np.float64) - w_vs[near]).max())
+    print(f"coincident, loops 0 and 1: max|err| {err:.3e} = {err / tol:.2f} of the bound {tol:.3e}")
+    assert err <= tol
 
 
 # ---- fairing -----------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """semigcn_amd.prepare on the device against the float64 restatement in tests/prepare_oracle.py: the smoothing rule (closed,
-open, non-manifold and isolated-vertex meshes), its reproducibility and invariants, the mean edge length, the scan mask,
+open, non-manifold and isolated-vertex meshes; hubs whose neighbour list is a tail, whole groups of four or both; zero
+weights next to a NaN; 255 and 256 faces on an edge), its reproducibility and invariants, the mean edge length, the scan mask,
 prepare_inputs -> train.MeshBatch, and the command line."""
 import json
 import os
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import holes_fixtures as HF
 import prepare_oracle as PO
 from semigcn_amd import synth
 
@@ -88,7 +90,6 @@ def bound(steps, d_max, vs):
 @pytest.mark.parametrize("steps", [1, 2, 30])
 @pytest.mark.parametrize("name", list(MESHES))
 def test_smoothing_vs_float64(name, steps):
-    from semigcn_amd import prepare
     vs, faces = MESHES[name]()
     d_max, C = PO.neighbour_lists(faces, vs.shape[0])
     if name == "fin":                                             # the blister's floor: two neighbours weigh 3, the others 2
@@ -98,16 +99,111 @@ def test_smoothing_vs_float64(name, steps):
         assert (C == 2).sum() >= 2 * (9 + 7) - 4                  # border vertices: two border edges each
     if name == "isolated":
         assert C[5] == 0
+    got = check_smoothing(name, vs, faces, steps)
+    if name == "isolated":
+        assert np.array_equal(got[5], vs[5])
+
+
+def check_smoothing(label, vs, faces, steps, rows=None):
+    """The device against the oracle on ``rows`` (default: every vertex), within ``bound`` built from those rows.  Returns the
+    device result."""
+    from semigcn_amd import prepare
+    rows = np.arange(vs.shape[0]) if rows is None else rows
+    d_max, _ = PO.neighbour_lists(faces, vs.shape[0])
     want = PO.smooth(vs, faces, steps)
     got = prepare.laplacian_smooth(dev(vs), dev(faces), steps=steps)
     assert got.dtype == torch.float32 and tuple(got.shape) == vs.shape
-    err = float(np.abs(got.cpu().numpy().astype(np.float64) - want).max())
-    b = bound(steps, d_max, vs)
-    print(f"{name} steps={steps}: max|err| {err:.3e}  bound {b:.3e}  d_max {d_max}")
+    got = got.cpu().numpy()
+    assert np.isfinite(got[rows]).all() and np.isfinite(want[rows]).all()
+    err = float(np.abs(got[rows].astype(np.float64) - want[rows]).max())
+    b = bound(steps, d_max, vs[rows])
+    print(f"{label} steps={steps}: max|err| {err:.3e}  bound {b:.3e}  d_max {d_max}")
     assert err <= b
-    assert float(np.abs(want - vs).max()) > 100 * b               # the step moved the mesh by far more than the bound
-    if name == "isolated":
-        assert np.array_equal(got.cpu().numpy()[5], vs[5])
+    assert float(np.abs(want[rows] - vs[rows]).max()) > 100 * b   # the step moved the mesh by far more than the bound
+    return got
+
+
+# ---- the neighbour loop: groups of four and a tail, zero weights, the 8-bit weight -----------------------------------------
+def valences(faces, V):
+    a, b = faces.reshape(-1), faces[:, [1, 2, 0]].reshape(-1)
+    return np.bincount(np.unique(np.concatenate([a * V + b, b * V + a])) // V, minlength=V)
+
+
+def grid_cut(V):
+    """grid_patch(3, 86) has 258 vertices; without the last ones and their faces V = 255, 256, 257: one lane either side of a
+    block of 256."""
+    vs, faces = grid_patch(3, 86)
+    return vs[:V].copy(), faces[(faces < V).all(1)]
+
+
+@pytest.mark.parametrize("steps", [1, 5])
+@pytest.mark.parametrize("n", [3, 4, 5, 7, 8, 9, 64, 300])
+def test_smoothing_hub_valences(n, steps):
+    """A hub's list of n neighbours: a tail only (3), one group of four and no tail (4), a group and a tail (5, 7), two groups
+    (8), two and a tail (9), many (64, 300).  Every rim vertex is interior with exactly four neighbours."""
+    vs, faces = HF.bipyramid(n)
+    d, (d_max, C) = valences(faces, n + 2), PO.neighbour_lists(faces, n + 2)
+    assert d[:n].tolist() == [4] * n and d[n:].tolist() == [n, n] and d_max == max(n, 4)
+    assert np.array_equal(C, 2.0 * d)                             # closed: every edge has two faces, no vertex is a border vertex
+    check_smoothing(f"bipyramid({n})", vs, faces, steps)
+
+
+@pytest.mark.parametrize("steps", [1, 5])
+def test_smoothing_open_fan_of_300(steps):
+    """Every rim vertex is a border vertex: its two rim edges weigh 1, its hub edge (two faces) weighs 0.  The hub is interior
+    with 300 neighbours of weight 2."""
+    vs, faces = HF.fans([300])
+    d, (d_max, C) = valences(faces, 301), PO.neighbour_lists(faces, 301)
+    assert d[:300].tolist() == [3] * 300 and d[300] == 300 == d_max
+    assert C[:300].tolist() == [2.0] * 300 and C[300] == 600.0
+    check_smoothing("fans([300])", vs, faces, steps)
+
+
+@pytest.mark.parametrize("steps", [1, 5])
+def test_zero_weight_drops_the_term_whatever_the_neighbour_holds(steps):
+    """The same fan with a NaN hub: 0 * NaN would be NaN, so a rim vertex stays finite only if its zero-weight term is not
+    formed at all.  The rim equals the oracle, whose border vertices never read the hub."""
+    vs, faces = HF.fans([300])
+    vs[300] = np.nan
+    got = check_smoothing("fans([300]), NaN hub", vs, faces, steps, rows=np.arange(300))
+    assert np.isnan(got[300]).all()
+
+
+@pytest.mark.parametrize("steps", [1, 5])
+def test_smoothing_weight_four_without_a_border(steps):
+    import manifold_oracle as MO
+    vs, faces = MO.two_tetrahedra_sharing_an_edge()
+    d, (d_max, C) = valences(faces, 6), PO.neighbour_lists(faces, 6)
+    assert d.tolist() == [5, 5, 3, 3, 3, 3] and C.tolist() == [12.0, 12.0, 6.0, 6.0, 6.0, 6.0]      # 4 + 4 * 2 on the shared edge's ends
+    check_smoothing("two tetrahedra on an edge", vs, faces, steps)
+
+
+@pytest.mark.parametrize("steps", [1, 5])
+def test_smoothing_255_faces_on_an_edge(steps):
+    """The largest count the 8-bit weight holds.  Both ends of the edge have 256 neighbours, 64 full groups of four: 255
+    border edges of weight 1 and the shared edge, first in the list, of weight 0."""
+    import manifold_oracle as MO
+    vs, faces = MO.fan(255)
+    d, (d_max, C) = valences(faces, 257), PO.neighbour_lists(faces, 257)
+    assert d[:2].tolist() == [256, 256] and d[2:].tolist() == [2] * 255 and d_max == 256
+    assert C[:2].tolist() == [255.0, 255.0] and C[2:].tolist() == [2.0] * 255
+    check_smoothing("fan(255)", vs, faces, steps)
+
+
+def test_256_faces_on_an_edge_are_refused():
+    import manifold_oracle as MO
+    from semigcn_amd import capi, prepare
+    vs, faces = MO.fan(256)
+    with pytest.raises(capi.SemigcnLibraryError, match="more than 255 faces"):
+        prepare.laplacian_smooth(dev(vs), dev(faces), steps=1)
+
+
+@pytest.mark.parametrize("steps", [1, 5])
+@pytest.mark.parametrize("V", [255, 256, 257])
+def test_smoothing_one_lane_either_side_of_a_block(V, steps):
+    vs, faces = grid_cut(V)
+    assert vs.shape[0] == V and int(faces.max()) == V - 1
+    check_smoothing(f"grid cut to {V}", vs, faces, steps)
 
 
 def test_zero_steps_is_a_copy_and_negative_steps_raise():
