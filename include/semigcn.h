@@ -522,6 +522,49 @@ SG_API int sg_normal_agreement(const float* vs_a, const int64_t* faces_a, const 
                                void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Point-to-plane registration of a point set onto a surface: the two device
+ * steps of one iteration of semigcn_amd/align.py ("The rule" there is the
+ * specification; the reference leaves the step to MeshLab by hand).  The host
+ * drives the iterations: transform, sg_surface_query, accumulate, one copy of
+ * 40 doubles, a 6 x 6 or 7 x 7 solve.  csrc/mesh_align.hip.
+ *
+ * pose: 12 doubles on the HOST, read before the call returns: M row-major,
+ * then t.  x = M p + t is ((M_r0 p_x + M_r1 p_y) + M_r2 p_z) + t_r per row r in
+ * float64 on the float32 point, plain multiplies and adds in that order.
+ * Limits: N < 2^31.  A null pointer, a negative size, a size beyond that or a
+ * NaN max_dist gives SG_ERR_INVALID before the device is touched; N == 0
+ * returns SG_OK without a launch (and writes nothing).
+ *
+ * sg_align_transform: out float32 [N,3] = x rounded to float32 once, for pts
+ *   float32 [N,3] (device); out may be pts itself.  Non-finite values
+ *   propagate.  Asynchronous.
+ * sg_align_accumulate: the normal equations of one Gauss-Newton step.  vs
+ *   float32 [V,3] and faces int64 [F,3] are the target's, as sg_surface_raycast
+ *   takes them; pts float32 [N,3] the UNtransformed source points; closest
+ *   float32 [N,3], face int32 [N] and dist float32 [N] what sg_surface_query
+ *   returned for the sg_align_transform of pts.  Per row i, in float64: x (not
+ *   rounded); N_f = (B-A) x (C-A) of face face[i] on the float32 coordinates,
+ *   each component u_y v_z - u_z v_y; nn = (N_x^2 + N_y^2) + N_z^2; n = N_f /
+ *   sqrt(nn).  The row is SKIPPED if face[i] is negative or 0x7fffffff, x is
+ *   not finite or nn == 0; else REJECTED AS FAR if (double)dist[i] > max_dist
+ *   (an infinite max_dist rejects nothing); else USED: e = x - closest, r =
+ *   (n_x e_x + n_y e_y) + n_z e_z, J = (x x n, n, n.x) -- seven entries, J_6
+ *   exactly 0 when with_scale == 0.  out (device, 40 doubles): [0..27] sum J_j
+ *   J_k for j <= k in row-major upper-triangle order, [28..34] sum J_j r, [35]
+ *   sum r^2, [36] sum (double)dist^2 -- over the used rows --, [37] rows used,
+ *   [38] rows rejected as far, [39] rows skipped.  partial: device scratch of
+ *   40 * SG_REDUCE_BLOCKS doubles.  Block partials over fixed runs of
+ *   consecutive indices, added in block order, as sg_distance_stats: no
+ *   floating-point atomics, two runs give identical bytes.  A face[i] >= F
+ *   that is not the "no face" value is not checked (as sg_normal_agreement).
+ *   Asynchronous.
+ * ------------------------------------------------------------------------- */
+SG_API int sg_align_transform(const float* pts, int64_t N, const double* pose, float* out, void* stream);
+SG_API int sg_align_accumulate(const float* vs, int64_t V, const int64_t* faces, int64_t F, const float* pts, int64_t N,
+                               const double* pose, const float* closest, const int32_t* face, const float* dist,
+                               double max_dist, int with_scale, double* partial, double* out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Network inputs from a remeshed scan -- replaces the tail of
  * preprocess/prepare.py: edge_based_scaling (:48-52) and smooth (:110-114,
  * pymeshlab's laplacian_smooth with stepsmoothnum=30, cotangentweight=False).

@@ -219,6 +219,9 @@ _SIGNATURES = {
     "sg_distance_stats": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
     "sg_normal_agreement": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                     c_void_p]),
+    "sg_align_transform": (c_int, [c_void_p, c_int64, POINTER(c_double), c_void_p, c_void_p]),
+    "sg_align_accumulate": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, POINTER(c_double), c_void_p,
+                                    c_void_p, c_void_p, c_double, c_int, c_void_p, c_void_p, c_void_p]),
     "sg_edge_length_blocks": (c_int64, [c_int64]),
     "sg_mean_edge_length": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sg_smooth_create": (c_int, [c_void_p, c_int64, c_int64, c_void_p, POINTER(c_void_p)]),
@@ -1752,6 +1755,84 @@ def normal_agreement(vs_a: torch.Tensor, faces_a: torch.Tensor, face_a: torch.Te
         with _on_device(vs_a.device):
             _check(load().sg_normal_agreement(_ptr(vs_a), _ptr(faces_a), _ptr(face_a), _ptr(vs_b), _ptr(faces_b), _ptr(face_b),
                                               face_a.shape[0], _ptr(part), _ptr(out), _stream(vs_a)), "sg_normal_agreement")
+    return out
+
+
+ALIGN_SUMS = 40                              # doubles sg_align_accumulate writes: A 28, g 7, sum r^2, sum d^2, 3 counts
+
+
+def _pose_arg(pose):
+    """The 12 host doubles of a pose (M row-major, then t) from a 4 x 4 (or 3 x 4) matrix or 12 values."""
+    import numpy as np
+    a = np.asarray(pose, dtype=np.float64)
+    if a.shape in ((4, 4), (3, 4)):
+        a = np.concatenate([a[:3, :3].reshape(-1), a[:3, 3]])
+    if a.shape != (12,):
+        raise ValueError(f"pose must be a 4 x 4 matrix or 12 values (M row-major, then t), got shape {a.shape}")
+    return (c_double * 12)(*a.tolist())
+
+
+def _points_arg(t: torch.Tensor, name: str, like: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _require_device(t, name)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3:
+        raise SemigcnLibraryError(f"{name} must be float32 [N, 3], got {t.dtype} {tuple(t.shape)}")
+    if like is not None and (t.device != like.device or t.shape != like.shape):
+        raise SemigcnLibraryError(f"{name} must be [{like.shape[0]}, 3] on {like.device}, got {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def align_transform(pts: torch.Tensor, pose, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 [N, 3]: ``M p + t`` in float64 rounded once (sg_align_transform).  ``pose``: a 4 x 4 matrix or 12 host
+    values; ``out`` may be ``pts`` itself (both contiguous)."""
+    pose = _pose_arg(pose)
+    _points_arg(pts, "pts")
+    if out is None:
+        pts = pts.contiguous()
+        out = torch.empty_like(pts)
+    else:
+        _points_arg(out, "out", pts)
+        if not (pts.is_contiguous() and out.is_contiguous()):
+            raise SemigcnLibraryError("align_transform: pts and out must be contiguous")
+    with _on_device(pts.device):
+        _check(load().sg_align_transform(_ptr(pts), pts.shape[0], pose, _ptr(out), _stream(pts)), "sg_align_transform")
+    return out
+
+
+def align_accumulate(vs: torch.Tensor, faces: torch.Tensor, pts: torch.Tensor, pose, closest: torch.Tensor, face: torch.Tensor,
+                     dist: torch.Tensor, max_dist: float = math.inf, with_scale: bool = False,
+                     scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float64 [40] on the device (sg_align_accumulate): the normal equations of one point-to-plane step over the rows of
+    ``pts`` (untransformed) against the target ``(vs, faces)``, with ``closest`` / ``face`` / ``dist`` from the target's query
+    of the transformed points.  ``scratch``: float64 [40 * REDUCE_BLOCKS] to reuse between iterations."""
+    pose = _pose_arg(pose)
+    max_dist = float(max_dist)
+    if math.isnan(max_dist):
+        raise ValueError("max_dist is NaN")
+    _require_device(vs, "vs")
+    _require_device(faces, "faces")
+    vs, faces = _vs_arg(vs).contiguous(), _faces_arg(faces)
+    pts = _points_arg(pts, "pts").contiguous()
+    closest = _points_arg(closest, "closest", pts).contiguous()
+    N = pts.shape[0]
+    for t, name, dt in ((face, "face", torch.int32), (dist, "dist", torch.float32)):
+        _require_device(t, name)
+        if t.dtype != dt or t.dim() != 1 or t.shape[0] != N:
+            raise SemigcnLibraryError(f"{name} must be {dt} [{N}], got {t.dtype} {tuple(t.shape)}")
+    for t, name in ((faces, "faces"), (face, "face"), (dist, "dist"), (pts, "pts")):
+        if t.device != vs.device:
+            raise SemigcnLibraryError(f"{name} on {t.device}, vs on {vs.device}")
+    face, dist = face.contiguous(), dist.contiguous()
+    out = torch.zeros(ALIGN_SUMS, dtype=torch.float64, device=vs.device)
+    if N:
+        if scratch is None:
+            scratch = torch.empty(ALIGN_SUMS * REDUCE_BLOCKS, dtype=torch.float64, device=vs.device)
+        elif scratch.dtype != torch.float64 or scratch.numel() < ALIGN_SUMS * REDUCE_BLOCKS or scratch.device != vs.device \
+                or not scratch.is_contiguous():
+            raise SemigcnLibraryError(f"scratch must be float64 [{ALIGN_SUMS * REDUCE_BLOCKS}] on {vs.device}")
+        with _on_device(vs.device):
+            _check(load().sg_align_accumulate(_ptr(vs), vs.shape[0], _ptr(faces), faces.shape[0], _ptr(pts), N, pose,
+                                              _ptr(closest), _ptr(face), _ptr(dist), max_dist, int(bool(with_scale)),
+                                              _ptr(scratch), _ptr(out), _stream(vs)), "sg_align_accumulate")
     return out
 
 

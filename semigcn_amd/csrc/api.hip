@@ -589,6 +589,27 @@ SG_API int sg_normal_agreement(const float* vs_a, const int64_t* faces_a, const 
   return normal_agreement(vs_a, faces_a, face_a, vs_b, faces_b, face_b, N, partial, out, (hipStream_t)stream);
 }
 
+// point-to-plane registration (semigcn_amd/align.py, "The rule"): csrc/mesh_align.hip
+SG_API int sg_align_transform(const float* pts, int64_t N, const double* pose, float* out, void* stream) {
+  SG_REQUIRE(N >= 0 && N < ((int64_t)1 << 31), "sg_align_transform: N must be in [0, 2^31), got %lld", (long long)N);
+  SG_REQUIRE(pose != nullptr, "sg_align_transform: null pose");
+  if (N == 0) return SG_OK;
+  SG_REQUIRE(pts && out, "sg_align_transform: null pointer");
+  return align_transform(pts, N, pose, out, (hipStream_t)stream);
+}
+
+SG_API int sg_align_accumulate(const float* vs, int64_t V, const int64_t* faces, int64_t F, const float* pts, int64_t N,
+                               const double* pose, const float* closest, const int32_t* face, const float* dist,
+                               double max_dist, int with_scale, double* partial, double* out, void* stream) {
+  SG_REQUIRE(N >= 0 && N < ((int64_t)1 << 31), "sg_align_accumulate: N must be in [0, 2^31), got %lld", (long long)N);
+  SG_REQUIRE(V >= 0 && F >= 0, "sg_align_accumulate: negative size (V = %lld, F = %lld)", (long long)V, (long long)F);
+  SG_REQUIRE(pose != nullptr, "sg_align_accumulate: null pose");
+  SG_REQUIRE(!(max_dist != max_dist), "sg_align_accumulate: max_dist is NaN");
+  if (N == 0) return SG_OK;
+  SG_REQUIRE(vs && faces && pts && closest && face && dist && partial && out, "sg_align_accumulate: null pointer");
+  return align_accumulate(vs, faces, pts, N, pose, closest, face, dist, max_dist, with_scale, partial, out, (hipStream_t)stream);
+}
+
 // preprocess/prepare.py:48-52 (edge_based_scaling) and :110-114 (smooth): csrc/mesh_smooth.hip
 SG_API int64_t sg_edge_length_blocks(int64_t E) { return E >= 0 ? edge_length_blocks(E) : -1; }
 

@@ -1,9 +1,9 @@
-// What the mesh stages (mesh_prep, mesh_smooth, mesh_fill, mesh_parts, mesh_manifold, mesh_remesh, mesh_dist, mesh_isect, mesh_fair, mesh_sample, mesh_denoise, mesh_ray) share on the host
+// What the mesh stages (mesh_prep, mesh_smooth, mesh_fill, mesh_parts, mesh_manifold, mesh_remesh, mesh_dist, mesh_isect, mesh_fair, mesh_sample, mesh_denoise, mesh_ray, mesh_align) share on the host
 // side: typed device buffers that own their memory, the launch geometry, the bit count behind the radix-sort ranges, the
 // exclusive scan, and the kernels and the one device helper that were literal copies.  The rule that goes with it: device
 // memory of a plan or of a call is a typed member or local that frees itself -- never a raw pointer on a hand-kept free list.
 // No floating-point code belongs here: mesh_isect.hip, mesh_remesh.hip, mesh_manifold.hip, mesh_fair.hip, mesh_sample.hip,
-// mesh_denoise.hip and mesh_ray.hip are built with -ffp-contract=off, the others not.
+// mesh_denoise.hip, mesh_ray.hip and mesh_align.hip are built with -ffp-contract=off, the others not.
 #pragma once
 #include <hipcub/hipcub.hpp>
 
@@ -16,6 +16,15 @@ namespace sg {
 constexpr int kThreads = 256;
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+
+// The runs of the deterministic reductions (sg_distance_stats, sg_normal_agreement, sg_align_accumulate): at most
+// SG_REDUCE_BLOCKS blocks, block b sums the rows [b * chunk, (b + 1) * chunk), chunk a multiple of kThreads
+inline int blocks_of(int64_t N) { return N == 0 ? 1 : (int)(blocks_for(N) < (unsigned)SG_REDUCE_BLOCKS ? blocks_for(N) : SG_REDUCE_BLOCKS); }
+
+inline int64_t chunk_for(int64_t N, int nb) {
+  const int64_t c = (N + nb - 1) / nb;
+  return (c + kThreads - 1) / kThreads * kThreads;
+}
 
 // bits needed for a value below n (at least 1, at most cap): the end bit of a radix sort over such values
 inline int bits_for(uint64_t n, int cap) {

@@ -222,15 +222,7 @@ __global__ void draw_sorted(const float* __restrict__ tri, const uint32_t* __res
   emit(tri, (int)keys[j], draw_k(k, seed, W), k, j, points, face, bary, index);
 }
 
-// ---- reductions: K values per index, block partials in index order ----
-
-// rows of the run of block b: [b * chunk, (b + 1) * chunk), chunk a multiple of kThreads
-inline int64_t chunk_for(int64_t N, int nb) {
-  const int64_t c = (N + nb - 1) / nb;
-  return (c + kThreads - 1) / kThreads * kThreads;
-}
-
-inline int blocks_of(int64_t N) { return N == 0 ? 1 : (int)(blocks_for(N) < (unsigned)SG_REDUCE_BLOCKS ? blocks_for(N) : SG_REDUCE_BLOCKS); }
+// ---- reductions: K values per index, block partials in index order (the runs: mesh_common.h, chunk_for / blocks_of) ----
 
 // v[0] is a maximum, v[1 .. K) are sums; thread 0 of the block writes part[K * block + k]
 template <int K>

@@ -358,6 +358,11 @@ int sampler_draw(const sg_sampler* s, uint64_t seed, uint64_t offset, int64_t N,
 int distance_stats(const float* dist, int64_t N, float tau, double* partial, double* out, hipStream_t stream);
 int normal_agreement(const float* vs_a, const int64_t* faces_a, const int32_t* face_a, const float* vs_b, const int64_t* faces_b,
                      const int32_t* face_b, int64_t N, double* partial, double* out, hipStream_t stream);
+// csrc/mesh_align.hip
+int align_transform(const float* pts, int64_t N, const double* pose, float* out, hipStream_t stream);
+int align_accumulate(const float* vs, const int64_t* faces, const float* pts, int64_t N, const double* pose, const float* closest,
+                     const int32_t* face, const float* dist, double max_dist, int with_scale, double* partial, double* out,
+                     hipStream_t stream);
 
 int launch_mesh_loss_bwd_corners(const float* pos, const int64_t* faces, const float* tfn, const float* fkeep, const float* g,
                                  int64_t F, float* corner, hipStream_t stream);

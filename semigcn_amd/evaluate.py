@@ -21,7 +21,9 @@ Command line::
 prints one JSON line with ``hd_all``, ``hd_hole``, ``n_hole`` and ``diag``.  With ``--sampled N [--seed S] [--tau T]
 [--order face|draw]`` the line also carries the two-sided sampled distance of ``surface_distance`` (``hausdorff``,
 ``chamfer``, their ``_rel``, ``max_ab`` .. ``rms_ba``, ``normal_consistency``) and the device time of its stages
-(``sample_ms``, ``query_ms``, ``stats_ms``); ``--org`` is then optional.
+(``sample_ms``, ``query_ms``, ``stats_ms``); ``--org`` is then optional.  With ``--align rigid|similarity`` ``out`` is first
+moved onto ``gt`` by ``semigcn_amd.align.align`` (both complete meshes; samples of ``out`` with ``--seed``) and ``org`` by
+the same matrix, and the line gains ``align_scale``, ``align_iterations`` and ``align_converged``.
 
 Sampling rule
 -------------
@@ -304,13 +306,26 @@ def main(argv=None) -> int:
     ap.add_argument("--seed", type=int, default=0, help="sample stream of --sampled (gt -> out; out -> gt takes seed + 1)")
     ap.add_argument("--tau", type=float, help="with --sampled: also the share of samples within this distance")
     ap.add_argument("--order", choices=tuple(capi.SAMPLE_ORDERS), default="face", help="row order of the samples")
+    ap.add_argument("--align", choices=("rigid", "similarity"),
+                    help="first move out onto gt by point-to-plane ICP (semigcn_amd.align; with 'similarity' also a uniform "
+                         "scale) and org by the same matrix: for an out and org in another frame than gt")
     args = ap.parse_args(argv)
     gt, out = read_obj(args.gt), read_obj(args.out)
-    if args.org:
-        r = mesh_distance(gt, read_obj(args.org), out, real=args.real)
+    org = read_obj(args.org) if args.org else None
+    aligned = None
+    if args.align:
+        from . import align as _align             # imported here: that module imports this one
+        aligned = _align.align(out, gt, with_scale=args.align == "similarity", seed=args.seed)
+        out = (_align.apply(aligned.matrix, out[0]), out[1])
+        if org is not None:
+            org = (_align.apply(aligned.matrix, org[0]), org[1])
+    if org is not None:
+        r = mesh_distance(gt, org, out, real=args.real)
         res = {k: r[k] for k in ("hd_all", "hd_hole", "n_hole", "diag")}
     else:
         res = {"hd_all": simple_mesh_distance(gt, out)}
+    if aligned is not None:
+        res.update({"align_scale": aligned.scale, "align_iterations": aligned.iterations, "align_converged": aligned.converged})
     if args.sampled is not None:
         with Surface(gt) as gs, Surface(out) as os_:
             st = mesh_common.Stages(gs.device, True)

@@ -1,6 +1,6 @@
 """What the mesh stages share in Python: the sibling of csrc/mesh_common.h.
 
-``evaluate``, ``prepare``, ``holes``, ``manifold``, ``components``, ``repair``, ``remesh``, ``simplify``, ``denoise`` and ``render`` take their inputs, read and write their OBJ
+``evaluate``, ``prepare``, ``holes``, ``manifold``, ``components``, ``repair``, ``remesh``, ``simplify``, ``denoise``, ``render`` and ``align`` take their inputs, read and write their OBJ
 files and time their stages through this module, and through nothing of each other's that starts with an underscore.
 
 The lifetime rule of the objects those stages build (``capi.SmoothPlan`` / ``FillPlan`` / ``FairPlan`` / ``PartsPlan`` / ``ManifoldPlan`` / ``RemeshPlan`` / ``SamplerPlan`` / ``VertexUpdatePlan``,
